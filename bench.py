@@ -2,7 +2,7 @@
 """Benchmark of the hot path on MI355X: BASELINE.json's metric
 "upscaled frames/sec (4x, 30 DDIM steps, 8-frame 320p clip)".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full pass of the hot path over one synthetic 8-frame 320x320 clip:
@@ -13,9 +13,12 @@ timed region starts.  With N > 1 every rank (one process per GPU) upscales its o
 independent, there is no data-path collective -> weak scaling; the timed region is
 bracketed by barrier + synchronize on both sides and the MAX over ranks is reported.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last timed
+step's output with --dump-outputs and prints the line; nothing else.  With --full the line also holds:
   roofline     dominant kernel (implicit-GEMM conv/linear): algorithmic FLOP / HIP-event time per
-               launch over the timed region vs the dense fp16 MFMA peak (2.5 PFLOP/s)
+               launch vs the dense fp16 MFMA peak (2.5 PFLOP/s), from one extra instrumented step, with
+               the per-kernel table (`kernel_breakdown`)
+  throughput_mode  two clips per GPU on concurrent HIP streams (N=1 only), timed after the headline
   cpu_baseline the oracle (CPU fp32 restatement of the reference path) timed on this host's cores on
                a bounded sample (N=1 only), extrapolated by FLOP — a reported baseline, not the target
 """
@@ -25,6 +28,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -33,6 +37,27 @@ sys.path.insert(0, os.path.join(ROOT, "upscale-a-video_amd"))
 METRIC = "upscaled frames/sec (4x, 30 DDIM steps, 8-frame 320p clip)"
 PEAK_TFLOPS_F16 = 2500.0        # dense fp16/bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBPS = 8000.0          # HBM3E spec peak (6.3 TB/s measured achievable), same guide
+DUMP_SAMPLE = 1 << 22           # --dump-outputs: elements kept of an output larger than DUMP_MAX_BYTES (16 MiB as float32)
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outputs, out_dir):
+    """Write each tensor of {name: tensor} as out_dir/<name>.npy in float32.  One that would exceed DUMP_MAX_BYTES is written
+    as out_dir/<name>_sample.npy instead: DUMP_SAMPLE elements of its flattened values at flat indices drawn from a fixed
+    seed, so the same shape gives the same sample positions in every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() * 4 > DUMP_MAX_BYTES:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            flat, name = flat[idx.to(flat.device)], name + "_sample"
+        else:
+            flat = flat.reshape(t.shape)
+        arr = flat.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
 
 
 def build_text_encoder(dev, dim, kind):
@@ -246,7 +271,17 @@ def main():
                     help="HIP events around EVERY kernel family inside the timed region (costs ~2 %%: 50 k event records of ~3 us "
                          "of GPU time per clip).  Default: only the dominant kernel (conv_gemm, what `roofline` needs) is timed there "
                          "and the per-kernel table comes from one extra, untimed, fully instrumented step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: `roofline` + `kernel_breakdown` (HIP events, one extra "
+                         "instrumented step), `throughput_mode` (two clips per GPU) and `cpu_baseline`; the --no-* switches above "
+                         "and the kernel-event placements apply to such a run.  Off: set up, warm up, time --steps steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the pipeline's `.images`, rank 0) as "
+                         "DIR/images.npy in float32, or, above 64 MB, as DIR/images_sample.npy: 4 Mi values at fixed seeded "
+                         "flat indices.  Inputs and weights are seeded: the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if (args.timed_kernel_events or args.all_kernel_events) and not args.full:
+        raise SystemExit("bench.py: --timed-kernel-events / --all-kernel-events place the HIP events of --full; add --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU (RCCL);
@@ -409,7 +444,7 @@ def main():
     for i in range(args.warmup):
         out = one_step(100 + i)
     barrier()
-    use_events = (not args.no_kernel_events) and rank == 0
+    use_events = args.full and (not args.no_kernel_events) and rank == 0
     all_events = args.all_kernel_events or bool(os.environ.get("UAV_BENCH_DETAIL"))
     # window-sharded steps hold collectives: an extra step on rank 0 alone would hang, so that mode keeps its events inside the timed region
     timed_events = use_events and (args.timed_kernel_events or args.all_kernel_events or args.shard_windows)
@@ -425,6 +460,8 @@ def main():
     elapsed = time.perf_counter() - t0
     peak_alloc, peak_reserved = torch.cuda.max_memory_allocated(dev), torch.cuda.max_memory_reserved(dev)
     ops.PROFILER.stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"images": out}, args.dump_outputs)
     timed_summary = ops.PROFILER.summary() if timed_events else None
     extra_summary = None
     if use_events and (overlapped or not timed_events or (not all_events and world == 1)):
@@ -444,7 +481,7 @@ def main():
     # kernels of the other.  Measured after the timed region (1 warm-up step + 2 timed steps of 2 clips); never the headline value.
     assert out.shape == (1, 3, args.frames, 4 * args.height, 4 * args.width) and bool(torch.isfinite(out).all())
     two_clip = None
-    if world == 1 and ncl == 1 and not args.no_throughput_mode and not args.shard_windows:
+    if args.full and world == 1 and ncl == 1 and not args.no_throughput_mode and not args.shard_windows:
         one_step(300, 2)
         torch.cuda.synchronize(); t2 = time.perf_counter()
         for i in range(2):
@@ -566,7 +603,7 @@ def main():
                                               "one extra fully instrumented step after the timed region (the timed region itself carries "
                                               + ("events around conv_gemm only" if timed_events else "no events") + "); launches / ms are per that one step")
             res["kernel_time_ms_per_step"] = total_s / table_steps * 1e3
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -152,8 +152,31 @@ def test_bench_help_renders():
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-800:]
-    for flag in ("--gpus", "--steps", "--warmup", "--unet-stream", "--shard-windows", "--overlap-streams", "--clips-per-step"):
+    for flag in ("--gpus", "--steps", "--warmup", "--unet-stream", "--shard-windows", "--overlap-streams", "--clips-per-step",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: a small output is written whole in float32; one above the byte cap as a sample at flat
+    indices from a fixed seed, the same positions in every run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("uav_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    small = torch.randn(1, 3, 2, 4, 4, dtype=torch.float16)
+    assert bench.dump_outputs({"images": small}, str(tmp_path / "a")) == {"images": [1, 3, 2, 4, 4]}
+    a = np.load(tmp_path / "a" / "images.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, small.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 500)
+    big = torch.randn(1, 3, 2, 40, 40)
+    for d in ("b", "c"):
+        assert bench.dump_outputs({"images": big}, str(tmp_path / d)) == {"images_sample": [500]}
+    b, c = np.load(tmp_path / "b" / "images_sample.npy"), np.load(tmp_path / "c" / "images_sample.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, c)
+    assert np.isin(b, big.numpy().ravel()).all() and len(np.unique(b)) > 400
+    assert not os.path.exists(tmp_path / "b" / "images.npy")
 
 
 def test_oracle_ddim_vs_golden():
