@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 6
+#define UAV_ABI_VERSION 7
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -510,6 +510,25 @@ int uav_frames_to_clip_f32(const void* frames_tchw, int32_t src_is_u8, float* cl
  * 't c h w -> t h w c', `.astype(np.uint8)` (truncation) (inference_upscale_a_video.py:357-359); C <= 4 */
 int uav_clip_to_frames_u8(const float* frames_tchw, void* frames_thwc_u8, int32_t t_len, int32_t c, int64_t hw,
                           void* stream);
+/* Planar 8-bit Y'CbCr (the payload of a YUV4MPEG2 file) <-> the tensors above, for the stand-alone front end (uav/cli.py).
+ * Colour conversion in 16.16 fixed point on int32, so every output is defined bit for bit; `coefs` is a HOST array the
+ * caller derives from (Kr, Kb, range) — uav.video_io.yuv_coefficients — and the kernels know no standard by name.
+ *
+ * planes Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) -> clip (3,T,H,W) fp32 in [-1,1]; any H, W >= 1.  coefs = {yo, iy, rcr,
+ * gcb, gcr, bcb}: y = (Y-yo)*iy, u = Cb-128, v = Cr-128 (chroma replicated over its 2x2 block),
+ * R = clamp((y + rcr*v + 32768) >> 16, 0, 255), G = clamp((y + gcb*u + gcr*v + 32768) >> 16, 0, 255),
+ * B = clamp((y + bcb*u + 32768) >> 16, 0, 255), then `(v/255. - 0.5) * 2` as uav_frames_to_clip_f32 */
+int uav_yuv420_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                           int32_t w, const int32_t* coefs, void* stream);
+/* the same for 4:4:4 planes: Cb, Cr (T,H,W) */
+int uav_yuv444_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                           int32_t w, const int32_t* coefs, void* stream);
+/* frames (T,3,H,W) fp32 in [-1,1], H and W even (else UAV_ESHAPE) -> planes Y (T,H,W), Cb, Cr (T,H/2,W/2).  The uint8 RGB
+ * value is formed as uav_clip_to_frames_u8 forms it; coefs = {fy[3], fcb[3], fcr[3], yo}:
+ * Y = clamp(((fy.rgb + 32768) >> 16) + yo, 0, 255); per 2x2 block Cb = clamp(((sum4 fcb.rgb + (1 << 17)) >> 18) + 128, 0, 255),
+ * Cr likewise with fcr */
+int uav_clip_to_yuv420_u8(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
+                          const int32_t* coefs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
 #   bench_c3 / bench_c4 / bench_2clips   configs[3] schedule on one GPU / one configs[4] tile with vae_video / two clips per GPU
 #   xpmc / attn512   SQ counters of the fused transformer / attention kernels (own --pmc pass);  d = 512 attention at L = 102 400, ring kernel vs attn512w
 #   bench1_lnfold / parity_lnfold   the LayerNorm-fold switch (UAV_LN_FOLD=1): clip time and the headline parity test
+#   yuvio           tools/bench_yuv_io.py: the Y4M front end's Y'CbCr kernels vs the RGB frame conversions, 20 warm launches each (kept copy: profiles/yuv_io_kernels.jsonl)
 # Environment: any UAV_* variable is passed through to every step.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
@@ -142,6 +143,7 @@ PY
       cat $L ;;
     attn512)  timeout 300 python $R/tools/bench_attn512.py 3 2>&1 | grep -v amdgpu.ids | tee $O/${TAG}_attn512.jsonl; UAV_ATTN512X=0 timeout 300 python $R/tools/bench_attn512.py 3 2>&1 | grep -v amdgpu.ids | tee -a $O/${TAG}_attn512.jsonl ;;
     digest)   timeout 200 python $R/tools/conv_digest.py 2>&1 | grep -v amdgpu.ids | tee $O/${TAG}_digest.log ;;
+    yuvio)    timeout 300 python $R/tools/bench_yuv_io.py --out $O/${TAG}_yuv_io_kernels.jsonl 2>&1 | grep -v amdgpu.ids ;;
     *)        echo "unknown step $step" ;;
   esac
 done

@@ -208,6 +208,247 @@ extern "C" int uav_clip_to_frames_u8(const float* frames_tchw, void* frames_thwc
     return uav_launch_status();
 }
 
+// ---- K13 (continued): planar Y'CbCr 4:2:0 / 4:4:4 uint8 <-> the clip / frame tensors, for the Y4M front end ---------------
+// Colour conversion in 16.16 fixed point on int32 (the host derives the coefficients from (Kr, Kb, range); every result is
+// defined bit for bit), fused with the normalisation of the two kernels above.  HBM-bound: a thread owns YUV_RUN pixels of
+// two adjacent rows, i.e. whole chroma samples, moves fp32 as 16-byte vectors and the planes as 4- / 8-byte words, and
+// falls back to scalar accesses for the tail of a row.  MODE 2: W % 8 == 0 (no tail); MODE 1: W % 4 == 0 (fp32 rows stay
+// 16-byte aligned, planes are moved as 4-byte luma and 2-byte chroma words, a 4-pixel tail is scalar); MODE 0: any W,
+// scalar throughout.  The launchers pick the mode from W and the pointers' alignment.  No LDS, no scratch.
+namespace {
+constexpr int YUV_RUN = 8;
+struct YuvInv { int yo, iy, rcr, gcb, gcr, bcb; };
+struct YuvFwd { int fy[3], fcb[3], fcr[3], yo; };
+
+UAV_DEVINL int yuv_clamp255(int v) { return min(max(v, 0), 255); }
+// uint8 value -> [-1,1], the expression of frames_to_clip_kernel
+UAV_DEVINL float yuv_u8_to_clip(int v) { return ((float)v / 255.0f - 0.5f) * 2.0f; }
+// [-1,1] -> uint8 value, the expression of clip_to_u8_kernel
+UAV_DEVINL int yuv_clip_to_u8(float x) {
+    float v = x / 2.0f + 0.5f;
+    v = fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f;
+    return (int)v;
+}
+UAV_DEVINL void yuv_to_rgb(const YuvInv& k, int yy, int u, int v, float& r, float& g, float& b) {
+    const int y = (yy - k.yo) * k.iy;
+    u -= 128; v -= 128;
+    r = yuv_u8_to_clip(yuv_clamp255((y + k.rcr * v + 32768) >> 16));
+    g = yuv_u8_to_clip(yuv_clamp255((y + k.gcb * u + k.gcr * v + 32768) >> 16));
+    b = yuv_u8_to_clip(yuv_clamp255((y + k.bcb * u + 32768) >> 16));
+}
+UAV_DEVINL int yuv_luma(const YuvFwd& k, int r, int g, int b) {
+    return yuv_clamp255(((k.fy[0] * r + k.fy[1] * g + k.fy[2] * b + 32768) >> 16) + k.yo);
+}
+// one chroma sample from the R, G, B sums of its 2x2 block (the four products summed before the one rounding)
+UAV_DEVINL int yuv_chroma(const int* f, int r, int g, int b) {
+    return yuv_clamp255(((f[0] * r + f[1] * g + f[2] * b + (1 << 17)) >> 18) + 128);
+}
+UAV_DEVINL uint32_t yuv_byte(uint32_t w, int j) { return (w >> (8 * j)) & 255u; }
+
+// planes Y (T,H,W), Cb / Cr (T,ch,cw) [ch = ceil(H/2), cw = ceil(W/2); C444: (T,H,W)] -> clip (3,T,H,W) fp32
+template <int MODE, bool C444>
+__global__ __launch_bounds__(256) void yuv_to_clip_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ cbp,
+                                                          const unsigned char* __restrict__ crp, float* __restrict__ dst, int t_len,
+                                                          int h, int w, YuvInv k) {
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = (h + 1) / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int rows = min(2, h - y0), n = min(YUV_RUN, w - x0);
+    const int ch = C444 ? h : (h + 1) / 2, cw = C444 ? w : (w + 1) / 2;
+    const long long hw = (long long)h * w;
+    const unsigned char* ysrc = yp + ((long long)t * h + y0) * w + x0;
+    float* out = dst + ((long long)t * h + y0) * w + x0;                       // channel stride: t_len * hw
+    const long long cs = (long long)t_len * hw;
+    if (MODE > 0 && n == YUV_RUN) {
+        uint32_t cbw[2], crw[2];                                                // 4:2:0: word 0 only (4 samples, shared by both rows)
+        if (!C444) {
+            const long long co = ((long long)t * ch + ry) * cw + (x0 >> 1);
+            if (MODE == 2) {
+                cbw[0] = *reinterpret_cast<const uint32_t*>(cbp + co);
+                crw[0] = *reinterpret_cast<const uint32_t*>(crp + co);
+            } else {
+                const unsigned short* a = reinterpret_cast<const unsigned short*>(cbp + co);
+                const unsigned short* b = reinterpret_cast<const unsigned short*>(crp + co);
+                cbw[0] = (uint32_t)a[0] | ((uint32_t)a[1] << 16);
+                crw[0] = (uint32_t)b[0] | ((uint32_t)b[1] << 16);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r >= rows) break;
+            uint32_t yw[2];
+            if (MODE == 2) {
+                const uint2_t v = *reinterpret_cast<const uint2_t*>(ysrc + (long long)r * w);
+                yw[0] = v.x; yw[1] = v.y;
+            } else {
+                yw[0] = *reinterpret_cast<const uint32_t*>(ysrc + (long long)r * w);
+                yw[1] = *reinterpret_cast<const uint32_t*>(ysrc + (long long)r * w + 4);
+            }
+            if (C444) {
+                const long long co = ((long long)t * h + y0 + r) * w + x0;
+                cbw[0] = *reinterpret_cast<const uint32_t*>(cbp + co); cbw[1] = *reinterpret_cast<const uint32_t*>(cbp + co + 4);
+                crw[0] = *reinterpret_cast<const uint32_t*>(crp + co); crw[1] = *reinterpret_cast<const uint32_t*>(crp + co + 4);
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {                                       // 4 pixels = one 16-byte store per channel
+                float4_t R, G, B;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = q * 4 + j;
+                    const int u = (int)(C444 ? yuv_byte(cbw[q], j) : yuv_byte(cbw[0], px >> 1));
+                    const int v = (int)(C444 ? yuv_byte(crw[q], j) : yuv_byte(crw[0], px >> 1));
+                    float fr, fg, fb;
+                    yuv_to_rgb(k, (int)yuv_byte(yw[q], j), u, v, fr, fg, fb);
+                    R[j] = fr; G[j] = fg; B[j] = fb;
+                }
+                float* o = out + (long long)r * w + q * 4;
+                *reinterpret_cast<float4_t*>(o) = R;
+                *reinterpret_cast<float4_t*>(o + cs) = G;
+                *reinterpret_cast<float4_t*>(o + 2 * cs) = B;
+            }
+        }
+        return;
+    }
+    for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < n; ++j) {
+            const long long co = C444 ? ((long long)t * h + y0 + r) * w + x0 + j : ((long long)t * ch + ry) * cw + ((x0 + j) >> 1);
+            float fr, fg, fb;
+            yuv_to_rgb(k, ysrc[(long long)r * w + j], cbp[co], crp[co], fr, fg, fb);
+            float* o = out + (long long)r * w + j;
+            o[0] = fr; o[cs] = fg; o[2 * cs] = fb;
+        }
+}
+
+// frames (T,3,H,W) fp32 in [-1,1], H and W even -> planes Y (T,H,W), Cb / Cr (T,H/2,W/2)
+template <int MODE>
+__global__ __launch_bounds__(256) void clip_to_yuv420_kernel(const float* __restrict__ src, unsigned char* __restrict__ yp,
+                                                             unsigned char* __restrict__ cbp, unsigned char* __restrict__ crp, int h,
+                                                             int w, YuvFwd k) {
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = h / 2, cw = w / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int n = min(YUV_RUN, w - x0);                                         // even
+    const long long hw = (long long)h * w;
+    const float* in = src + (long long)t * 3 * hw + (long long)y0 * w + x0;    // channel stride: hw
+    unsigned char* yd = yp + (long long)t * hw + (long long)y0 * w + x0;
+    const long long co = ((long long)t * nry + ry) * cw + (x0 >> 1);
+    if (MODE > 0 && n == YUV_RUN) {
+        int sr[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint32_t yw[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const float* p = in + (long long)r * w + q * 4;
+                const float4_t R = *reinterpret_cast<const float4_t*>(p);
+                const float4_t G = *reinterpret_cast<const float4_t*>(p + hw);
+                const float4_t B = *reinterpret_cast<const float4_t*>(p + 2 * hw);
+                uint32_t word = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ir = yuv_clip_to_u8(R[j]), ig = yuv_clip_to_u8(G[j]), ib = yuv_clip_to_u8(B[j]);
+                    word |= (uint32_t)yuv_luma(k, ir, ig, ib) << (8 * j);
+                    sr[q * 2 + (j >> 1)] += ir; sg[q * 2 + (j >> 1)] += ig; sb[q * 2 + (j >> 1)] += ib;
+                }
+                yw[q] = word;
+            }
+            if (MODE == 2) {
+                uint2_t v; v.x = yw[0]; v.y = yw[1];
+                *reinterpret_cast<uint2_t*>(yd + (long long)r * w) = v;
+            } else {
+                *reinterpret_cast<uint32_t*>(yd + (long long)r * w) = yw[0];
+                *reinterpret_cast<uint32_t*>(yd + (long long)r * w + 4) = yw[1];
+            }
+        }
+        uint32_t cbw = 0, crw = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            cbw |= (uint32_t)yuv_chroma(k.fcb, sr[c], sg[c], sb[c]) << (8 * c);
+            crw |= (uint32_t)yuv_chroma(k.fcr, sr[c], sg[c], sb[c]) << (8 * c);
+        }
+        if (MODE == 2) {
+            *reinterpret_cast<uint32_t*>(cbp + co) = cbw;
+            *reinterpret_cast<uint32_t*>(crp + co) = crw;
+        } else {
+            unsigned short* a = reinterpret_cast<unsigned short*>(cbp + co);
+            unsigned short* b = reinterpret_cast<unsigned short*>(crp + co);
+            a[0] = (unsigned short)cbw; a[1] = (unsigned short)(cbw >> 16);
+            b[0] = (unsigned short)crw; b[1] = (unsigned short)(crw >> 16);
+        }
+        return;
+    }
+    for (int c = 0; c < n / 2; ++c) {                                           // one 2x2 block at a time
+        int r4 = 0, g4 = 0, b4 = 0;
+        for (int r = 0; r < 2; ++r)
+            for (int j = 0; j < 2; ++j) {
+                const float* p = in + (long long)r * w + c * 2 + j;
+                const int ir = yuv_clip_to_u8(p[0]), ig = yuv_clip_to_u8(p[hw]), ib = yuv_clip_to_u8(p[2 * hw]);
+                yd[(long long)r * w + c * 2 + j] = (unsigned char)yuv_luma(k, ir, ig, ib);
+                r4 += ir; g4 += ig; b4 += ib;
+            }
+        cbp[co + c] = (unsigned char)yuv_chroma(k.fcb, r4, g4, b4);
+        crp[co + c] = (unsigned char)yuv_chroma(k.fcr, r4, g4, b4);
+    }
+}
+
+inline bool yuv_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+inline int yuv_mode(int w, const void* f32, const void* y, const void* cb, const void* cr, bool c444) {
+    if (!yuv_aligned(f32, 16)) return 0;
+    if (w % 8 == 0 && yuv_aligned(y, 8) && yuv_aligned(cb, 4) && yuv_aligned(cr, 4)) return 2;
+    if (w % 4 == 0 && yuv_aligned(y, 4) && yuv_aligned(cb, c444 ? 4 : 2) && yuv_aligned(cr, c444 ? 4 : 2)) return 1;
+    return 0;
+}
+
+template <bool C444>
+int yuv_to_clip_launch(const void* y, const void* cb, const void* cr, float* clip, int32_t t_len, int32_t h, int32_t w,
+                       const int32_t* coefs, void* stream) {
+    if (!y || !cb || !cr || !clip || !coefs) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0) return UAV_ESHAPE;
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * ((h + 1) / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    const YuvInv k = {coefs[0], coefs[1], coefs[2], coefs[3], coefs[4], coefs[5]};
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    const unsigned char *yp = (const unsigned char*)y, *cbp = (const unsigned char*)cb, *crp = (const unsigned char*)cr;
+    switch (yuv_mode(w, clip, y, cb, cr, C444)) {
+    case 2: hipLaunchKernelGGL((yuv_to_clip_kernel<2, C444>), grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip, t_len, h, w, k); break;
+    case 1: hipLaunchKernelGGL((yuv_to_clip_kernel<1, C444>), grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip, t_len, h, w, k); break;
+    default: hipLaunchKernelGGL((yuv_to_clip_kernel<0, C444>), grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip, t_len, h, w, k);
+    }
+    return uav_launch_status();
+}
+}  // namespace
+
+extern "C" int uav_yuv420_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                                      int32_t w, const int32_t* coefs, void* stream) {
+    return yuv_to_clip_launch<false>(y, cb, cr, clip_cthw, t_len, h, w, coefs, stream);
+}
+
+extern "C" int uav_yuv444_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                                      int32_t w, const int32_t* coefs, void* stream) {
+    return yuv_to_clip_launch<true>(y, cb, cr, clip_cthw, t_len, h, w, coefs, stream);
+}
+
+extern "C" int uav_clip_to_yuv420_u8(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
+                                     const int32_t* coefs, void* stream) {
+    if (!frames_tchw || !y || !cb || !cr || !coefs) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0 || (h & 1) || (w & 1)) return UAV_ESHAPE;
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * (h / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    YuvFwd k;
+    for (int i = 0; i < 3; ++i) { k.fy[i] = coefs[i]; k.fcb[i] = coefs[3 + i]; k.fcr[i] = coefs[6 + i]; }
+    k.yo = coefs[9];
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    unsigned char *yp = (unsigned char*)y, *cbp = (unsigned char*)cb, *crp = (unsigned char*)cr;
+    switch (yuv_mode(w, frames_tchw, y, cb, cr, false)) {
+    case 2: hipLaunchKernelGGL(clip_to_yuv420_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k); break;
+    case 1: hipLaunchKernelGGL(clip_to_yuv420_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k); break;
+    default: hipLaunchKernelGGL(clip_to_yuv420_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k);
+    }
+    return uav_launch_status();
+}
+
 extern "C" int64_t uav_plane_stats_workspace_bytes(int32_t planes) { return (int64_t)planes * CF_CHUNKS * 2 * 8; }
 
 extern "C" int uav_plane_stats_f32(const float* x, int32_t planes, int64_t hw, float* mean_out, float* var_out, void* workspace,

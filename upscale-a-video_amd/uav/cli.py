@@ -1,0 +1,218 @@
+"""The engine's own upscaling program: video files in, 4x video files out, on one MI355X.
+
+    ffmpeg -i in.mp4 in.y4m                                                   # on the user's side: any container -> YUV4MPEG2
+    python upscale.py -i in.y4m -o results --pretrained pretrained_models/upscale_a_video
+    ffmpeg -i results/video/in_n120_g6_s30.y4m out.mp4
+
+(`python -m uav.cli` with `upscale-a-video_amd` on the path is the same program.)  It takes the options of the reference
+project's `inference_upscale_a_video.py` and does per video what that program does — `video_io.upscale_clip` — but reads
+and writes by itself: YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and
+directories of images in; `.y4m` (4:2:0) out, the colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`,
+`uav_clip_to_yuv420_u8`).  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
+each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
+caption text, default none.
+
+`--pretrained DIR` is the released checkpoint layout: vae/{vae_3d,vae_video}{_config.json,.bin},
+unet/unet_video{_config.json,.bin}, scheduler/, low_res_scheduler/, text_encoder/, tokenizer/ and, for `-p`,
+propagator/raft-things.pth.  There is no random-weight mode: bench.py is the tool for running without checkpoints.
+"""
+import argparse
+import os
+import sys
+import time
+from fractions import Fraction
+
+import torch
+
+
+class UserError(Exception):
+    """A problem with the command line or the files it names: reported as one line, exit status 2."""
+
+
+def _int_list(text):
+    return [int(v) for v in text.split(",") if v.strip() != ""]
+
+
+def _fps(text):
+    try:
+        value = Fraction(text.replace(":", "/"))
+    except (ValueError, ZeroDivisionError):
+        raise argparse.ArgumentTypeError(f"not a frame rate: {text!r} (e.g. 24, 29.97, 30000/1001)") from None
+    if value <= 0:
+        raise argparse.ArgumentTypeError("the frame rate must be positive")
+    return value
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="upscale.py", description="Upscale-A-Video on an MI355X: 4x video super-resolution, Y4M in and out.")
+    p.add_argument("-i", "--input_path", required=True, help="a .y4m / .npy file, a directory of images, or a directory of those")
+    p.add_argument("-o", "--output_path", default="./results", help="output folder (videos go to <out>/video)")
+    p.add_argument("--pretrained", required=True, metavar="DIR", help="released checkpoint directory (pretrained_models/upscale_a_video)")
+    p.add_argument("-n", "--noise_level", type=int, default=120, help="noise level [0, 200] applied to the input video")
+    p.add_argument("-g", "--guidance_scale", type=int, default=6, help="classifier-free guidance scale")
+    p.add_argument("-s", "--inference_steps", type=int, default=30, help="number of denoising steps")
+    p.add_argument("-p", "--propagation_steps", type=_int_list, default=[], help="comma list of steps after which latents are propagated")
+    p.add_argument("--prompt", default="", help="caption of the video (there is no captioner); --a_prompt is appended")
+    p.add_argument("--a_prompt", default="best quality, extremely detailed")
+    p.add_argument("--n_prompt", default="blur, worst quality")
+    p.add_argument("--use_video_vae", action="store_true")
+    p.add_argument("--color_fix", default="None", choices=["None", "AdaIn", "Wavelet"])
+    p.add_argument("--perform_tile", action="store_true")
+    p.add_argument("--tile_size", type=int, default=256)
+    p.add_argument("--save_image", action="store_true", help="also write PNG frames to <out>/frame/<name> (needs PIL)")
+    p.add_argument("--save_suffix", default="")
+    p.add_argument("--matrix", default="auto", choices=["auto", "bt601", "bt709"],
+                   help="Y'CbCr matrix; auto = BT.709 from 720 rows up, else BT.601, decided separately for input and output size")
+    p.add_argument("--seed", type=int, default=10)
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
+    p.add_argument("--dump-rgb", dest="dump_rgb", metavar="FILE", default=None,
+                   help="write the uint8 RGB frames (T,H,W,3) of the last video as .npy (tests, A/B runs)")
+    return p
+
+
+def _need(path, what):
+    if not os.path.exists(path):
+        raise UserError(f"{what} not found: {path}")
+    return path
+
+
+def load_pipeline(base, *, use_video_vae=False, with_propagator=False, device="cuda:0"):
+    """The released checkpoint directory -> (pipeline, raft or None): VAE fp32 and UNet `.half()` with strict=True, DDIM
+    scheduler, then low_res_scheduler / text encoder / tokenizer; RAFT and the propagator only when asked for."""
+    from models_video.autoencoder_kl_cond_video import AutoencoderKLVideo
+    from models_video.pipeline_upscale_a_video import VideoUpscalePipeline
+    from models_video.scheduling_ddim import DDIMScheduler
+    from models_video.unet_video import UNetVideoModel
+    if not os.path.isdir(base):
+        raise UserError(f"--pretrained: {base} is not a directory")
+    name = "vae_video" if use_video_vae else "vae_3d"
+    vae = AutoencoderKLVideo.from_config(_need(os.path.join(base, "vae", name + "_config.json"), "VAE config"))
+    vae.load_state_dict(torch.load(_need(os.path.join(base, "vae", name + ".bin"), "VAE weights"), map_location="cpu"), strict=True)
+    unet = UNetVideoModel.from_config(_need(os.path.join(base, "unet", "unet_video_config.json"), "UNet config"))
+    unet.load_state_dict(torch.load(_need(os.path.join(base, "unet", "unet_video.bin"), "UNet weights"), map_location="cpu"), strict=True)
+    unet = unet.half().eval()
+    scheduler = DDIMScheduler.from_config(_need(os.path.join(base, "scheduler", "scheduler_config.json"), "scheduler config"))
+    for sub in ("low_res_scheduler", "text_encoder", "tokenizer"):
+        _need(os.path.join(base, sub), f"{sub}/")
+    pipeline = VideoUpscalePipeline.from_pretrained(base, torch_dtype=torch.float16)
+    pipeline.vae, pipeline.unet, pipeline.scheduler = vae, unet, scheduler
+    raft = propagator = None
+    if with_propagator:
+        from models_video.RAFT.raft_bi import RAFT_bi
+        from models_video.propagation_module import Propagation
+        raft = RAFT_bi(_need(os.path.join(base, "propagator", "raft-things.pth"), "RAFT weights (needed by -p)"), device=device)
+        propagator = Propagation(4, learnable=False)
+    pipeline.propagator = propagator
+    return pipeline.to(device), raft
+
+
+def list_videos(path):
+    """`-i`: one file, one directory of images, or a directory whose .y4m / .npy files and image sub-directories are one
+    video each (sorted by name)."""
+    from .video_io import IMAGE_EXTENSIONS
+    if os.path.isfile(path):
+        return [path]
+    if not os.path.isdir(path):
+        raise UserError(f"input not found: {path}")
+    videos = []
+    for n in sorted(os.listdir(path)):
+        full = os.path.join(path, n)
+        if os.path.isfile(full) and n.lower().endswith((".y4m", ".npy")):
+            videos.append(full)
+        elif os.path.isdir(full) and any(m.lower().endswith(IMAGE_EXTENSIONS) for m in os.listdir(full)):
+            videos.append(full)
+    if not videos and any(n.lower().endswith(IMAGE_EXTENSIONS) for n in os.listdir(path)):
+        return [path]
+    if not videos:
+        raise UserError(f"no .y4m / .npy files or image directories in {path}")
+    return videos
+
+
+def _save_png(frames_u8, folder):
+    try:
+        from PIL import Image
+    except ImportError:
+        raise UserError("--save_image needs the PIL package (Pillow)") from None
+    os.makedirs(folder, exist_ok=True)
+    for i, frame in enumerate(frames_u8):
+        Image.fromarray(frame).save(os.path.join(folder, f"{i:04d}.png"))
+
+
+def _read(path):
+    from . import video_io
+    try:
+        return video_io.read_frames(path)
+    except (ValueError, OSError) as e:
+        raise UserError(str(e)) from None
+
+
+def run(args):
+    from . import tiling, video_io
+    videos = list_videos(args.input_path)
+    device = torch.device(args.device)
+    if device.type == "cuda" and not torch.cuda.is_available():
+        raise UserError(f"--device {args.device}: no GPU is visible")
+    first = _read(videos[0])                # before the checkpoints are loaded: an unreadable input fails at once
+    pipeline, raft = load_pipeline(args.pretrained, use_video_vae=args.use_video_vae, with_propagator=bool(args.propagation_steps),
+                                   device=device)
+    prompt = args.prompt + args.a_prompt
+    out_path = None
+    for index, path in enumerate(videos):
+        source, fps = first if index == 0 else _read(path)
+        first = None
+        name = os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
+        if isinstance(source, video_io.Y4MClip):
+            clip = video_io.preprocess_planes(source, device, args.matrix)
+            in_size = source.size
+        else:
+            frames = torch.from_numpy(source).permute(0, 3, 1, 2).contiguous()
+            clip = video_io.preprocess_frames(frames.to(device))
+            in_size = tuple(source.shape[1:3])
+        t, (h, w) = clip.shape[2], clip.shape[-2:]
+        tiles = len(tiling.tile_grid(h, w, args.tile_size)) if tiling.needs_tiling(h, w, args.perform_tile) else 1
+        generator = torch.Generator(device=device).manual_seed(args.seed)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        start = time.time()
+        output = video_io.upscale_clip(pipeline, clip, prompt=prompt, negative_prompt=args.n_prompt, raft=raft,
+                                       propagation_steps=args.propagation_steps, steps=args.inference_steps,
+                                       guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
+                                       perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator)
+        full_range = source.full_range if isinstance(source, video_io.Y4MClip) else True
+        matrix = video_io.auto_matrix(output.shape[-2]) if args.matrix == "auto" else args.matrix
+        y, cb, cr = video_io.postprocess_planes(output, video_io.yuv_coefficients(matrix, full_range))
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        seconds = time.time() - start
+        prop = "_p" + "_".join(map(str, args.propagation_steps)) if args.propagation_steps else ""
+        suffix = "_" + args.save_suffix if args.save_suffix else ""
+        save_name = f"{name}_n{args.noise_level}_g{args.guidance_scale}_s{args.inference_steps}{prop}{suffix}"
+        os.makedirs(os.path.join(args.output_path, "video"), exist_ok=True)
+        out_path = os.path.join(args.output_path, "video", save_name + ".y4m")
+        video_io.write_y4m(out_path, y, cb, cr, args.fps or fps or 24, full_range)
+        if args.save_image or (args.dump_rgb and index == len(videos) - 1):
+            rgb = video_io.postprocess_frames(output).cpu().numpy()
+            if args.save_image:
+                _save_png(rgb, os.path.join(args.output_path, "frame", save_name))
+            if args.dump_rgb and index == len(videos) - 1:
+                import numpy as np
+                with open(args.dump_rgb, "wb") as fh:
+                    np.save(fh, rgb)
+        print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {4 * h}x{4 * w}, {tiles} tile(s), "
+              f"{seconds:.2f} s -> {out_path}", flush=True)
+    return out_path
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    try:
+        run(args)
+    except UserError as e:
+        print(f"upscale.py: error: {e}", file=sys.stderr)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1322,3 +1322,48 @@ def clip_to_frames_u8(frames):
     out = torch.empty((t, h, w, c), dtype=torch.uint8, device=frames.device)
     _lib.check(lib.uav_clip_to_frames_u8(_p(frames), _p(out), t, c, h * w, _stream()), "uav_clip_to_frames_u8")
     return out
+
+
+def _coef_array(values, n, what):
+    import ctypes
+    values = [int(v) for v in values]
+    if len(values) != n or any(not -2 ** 31 <= v < 2 ** 31 for v in values):
+        raise _lib.UavError(f"{what}: {n} int32 coefficients expected")
+    return (ctypes.c_int32 * n)(*values)
+
+
+def yuv420_to_clip_f32(y, cb, cr, coefs, chroma444=False):
+    """Planar uint8 Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) [chroma444: (T,H,W)] -> clip (3,T,H,W) fp32 in [-1,1]: 16.16
+    fixed-point colour conversion + `(x/255. - 0.5)*2`, one pass.  `coefs`: video_io.yuv_coefficients(...)."""
+    lib = _lib.load()
+    for name, p in (("y", y), ("cb", cb), ("cr", cr)):
+        _req(p, torch.uint8, name)
+        if p.dim() != 3 or p.device != y.device:
+            raise _lib.UavError(f"yuv420_to_clip_f32: {name} must be a (T,H,W) plane stack on one device")
+    t, h, w = y.shape
+    cshape = (t, h, w) if chroma444 else (t, (h + 1) // 2, (w + 1) // 2)
+    if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
+        raise _lib.UavError(f"yuv420_to_clip_f32: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape}")
+    k = _coef_array(coefs.inverse, 6, "yuv420_to_clip_f32")
+    out = torch.empty((3, t, h, w), dtype=torch.float32, device=y.device)
+    fn = lib.uav_yuv444_to_clip_f32 if chroma444 else lib.uav_yuv420_to_clip_f32
+    _lib.check(fn(_p(y), _p(cb), _p(cr), _p(out), t, h, w, k, _stream()), "uav_yuv444_to_clip_f32" if chroma444 else "uav_yuv420_to_clip_f32")
+    return out
+
+
+def clip_to_yuv420_u8(frames, coefs):
+    """(T,3,H,W) fp32 in [-1,1], H and W even -> uint8 planes Y (T,H,W), Cb, Cr (T,H/2,W/2): the uint8 RGB value of
+    clip_to_frames_u8, 16.16 fixed-point colour conversion, chroma = rounded mean of its 2x2 block, one pass."""
+    lib = _lib.load()
+    _req(frames, torch.float32, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise _lib.UavError("clip_to_yuv420_u8: (T,3,H,W) fp32 expected")
+    t, _, h, w = frames.shape
+    if h % 2 or w % 2:
+        raise _lib.UavError(f"clip_to_yuv420_u8: H and W must be even for 4:2:0 planes, got {h}x{w} (UAV_ESHAPE)")
+    k = _coef_array(coefs.forward, 10, "clip_to_yuv420_u8")
+    y = torch.empty((t, h, w), dtype=torch.uint8, device=frames.device)
+    cb = torch.empty((t, h // 2, w // 2), dtype=torch.uint8, device=frames.device)
+    cr = torch.empty_like(cb)
+    _lib.check(lib.uav_clip_to_yuv420_u8(_p(frames), _p(y), _p(cb), _p(cr), t, h, w, k, _stream()), "uav_clip_to_yuv420_u8")
+    return y, cb, cr

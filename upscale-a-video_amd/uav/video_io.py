@@ -1,16 +1,39 @@
-"""Device-side halves of the reference CLI's frame I/O (`inference_upscale_a_video.py:180-187,357-359`).
+"""Frame I/O around `pipeline(...)`: the device-side conversions, a YUV4MPEG2 reader / writer and the
+per-video body of the upscaling program (`uav/cli.py`).
 
-Decoding / encoding video files and the LLaVA captioner stay with the CLI (host side: torchvision / imageio / transformers,
-none of which the engine replaces); what runs on the GPU around `pipeline(...)` is here as two calls, each one kernel pass
-instead of the CLI's chains of eager tensor ops over the whole clip (4K output: 5 passes over 3.2 GB):
+Two kernel passes mirror what the reference CLI does with chains of eager tensor ops over the whole clip
+(`inference_upscale_a_video.py:180-187,357-359`; 4K output: 5 passes over 3.2 GB):
 
     clip = preprocess_frames(frames)        # (T,C,H,W) 0..255 -> (1,C,T,h,w) fp32 in [-1,1], >= 1280-px inputs area-pooled /4
     video = postprocess_frames(output)      # (T,C,H,W) in [-1,1] -> (T,H,W,C) uint8, ready for imageio.mimwrite
+
+and two more take the place of a decoder / encoder's colour conversion for the one container the engine reads and writes
+itself, YUV4MPEG2 (`.y4m`: uncompressed planar 8-bit Y'CbCr, what `ffmpeg -i in.mp4 in.y4m` / `ffmpeg -i out.y4m out.mp4`
+produce and eat), in 16.16 fixed point so that every byte is defined (csrc/colorfix.hip, K13):
+
+    clip = preprocess_planes(read_y4m(path), device)        # planes -> (1,3,T,h,w), same normalisation and pooling
+    y, cb, cr = postprocess_planes(output, coefs)           # (T,3,H,W) in [-1,1] -> 4:2:0 planes; write_y4m(path, y, cb, cr, ...)
+
+Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
+import os
+from collections import namedtuple
+from fractions import Fraction
+
 import torch
 
 from . import engine as E
 from . import ops
+
+# integer colour-conversion table: `forward` = fy[3], fcb[3], fcr[3], yo (RGB -> Y'CbCr), `inverse` = yo, iy, rcr, gcb, gcr, bcb
+YuvCoefs = namedtuple("YuvCoefs", "matrix full_range forward inverse")
+# a decoded .y4m file: uint8 numpy planes y (T,H,W), cb / cr (T,ceil(H/2),ceil(W/2)) [colorspace 'C444': (T,H,W)], fps a Fraction
+# or None, size (H, W), the file's colour-space tag ('' when it has none) and its range
+Y4MClip = namedtuple("Y4MClip", "y cb cr fps size colorspace full_range")
+
+_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+_CHROMA_420 = ("C420jpeg", "C420mpeg2", "C420paldv", "C420")
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
 
 def preprocess_frames(frames: torch.Tensor) -> torch.Tensor:
@@ -18,10 +41,14 @@ def preprocess_frames(frames: torch.Tensor) -> torch.Tensor:
     `unsqueeze(0)` + `rearrange('b t c h w -> b c t h w')` (inference_upscale_a_video.py:180-187)."""
     with E.device_guard(frames):
         clip = ops.frames_to_clip_f32(frames.contiguous())                      # (C,T,H,W)
-        h, w = clip.shape[-2:]
-        if h >= 1280 and w >= 1280:
-            clip = ops.resize_area_f32(clip, int(h // 4), int(w // 4))
-        return clip.unsqueeze(0)
+        return _pool_large(clip).unsqueeze(0)
+
+
+def _pool_large(clip):
+    h, w = clip.shape[-2:]
+    if h >= 1280 and w >= 1280:
+        clip = ops.resize_area_f32(clip, int(h // 4), int(w // 4))
+    return clip
 
 
 def postprocess_frames(output: torch.Tensor) -> torch.Tensor:
@@ -29,3 +56,198 @@ def postprocess_frames(output: torch.Tensor) -> torch.Tensor:
     stays on the device — `.cpu().numpy()` is the caller's (one 1-byte-per-value copy instead of an fp32 one)."""
     with E.device_guard(output):
         return ops.clip_to_frames_u8(output.float().contiguous())
+
+
+# ------------------------------------------------------------------------------------------------
+# Y'CbCr: integer coefficients, the two device passes
+def yuv_coefficients(matrix: str, full_range: bool) -> YuvCoefs:
+    """16.16 fixed-point tables of both directions for `matrix` in 'bt601' / 'bt709'.  With Kg = 1-Kr-Kb and (ys, yo, cs) =
+    (255, 0, 255) for full range, (219, 16, 224) for limited range, every entry is round(x * 65536) of the textbook value."""
+    if matrix not in _KR_KB:
+        raise ValueError(f"matrix must be one of {sorted(_KR_KB)}, got {matrix!r}")
+    kr, kb = _KR_KB[matrix]
+    kg = 1.0 - kr - kb
+    ys, yo, cs = (255, 0, 255) if full_range else (219, 16, 224)
+
+    def r(x):
+        return int(round(x * 65536))
+    fy = [r(kr * ys / 255), r(kg * ys / 255), r(kb * ys / 255)]
+    fcb = [r(-kr / (2 * (1 - kb)) * cs / 255), r(-kg / (2 * (1 - kb)) * cs / 255), r(0.5 * cs / 255)]
+    fcr = [r(0.5 * cs / 255), r(-kg / (2 * (1 - kr)) * cs / 255), r(-kb / (2 * (1 - kr)) * cs / 255)]
+    iy, rcr, bcb = r(255 / ys), r(2 * (1 - kr) * 255 / cs), r(2 * (1 - kb) * 255 / cs)
+    gcb, gcr = r(-2 * kb * (1 - kb) / kg * 255 / cs), r(-2 * kr * (1 - kr) / kg * 255 / cs)
+    return YuvCoefs(matrix, bool(full_range), tuple(fy + fcb + fcr + [yo]), (yo, iy, rcr, gcb, gcr, bcb))
+
+
+def auto_matrix(rows: int) -> str:
+    """The usual convention for untagged material: BT.709 from 720 rows up, BT.601 below."""
+    return "bt709" if rows >= 720 else "bt601"
+
+
+def preprocess_planes(clip: Y4MClip, device, matrix: str = "auto") -> torch.Tensor:
+    """A decoded .y4m clip -> (1,3,T,h,w) fp32 in [-1,1] on `device`: what `preprocess_frames` returns for the uint8 RGB
+    frames a decoder with the fixed-point arithmetic of `uav_yuv420_to_clip_f32` would have produced (colour conversion
+    and normalisation are one pass over 1.5 bytes per pixel; the >= 1280-px area pooling follows as there)."""
+    coefs = yuv_coefficients(auto_matrix(clip.size[0]) if matrix == "auto" else matrix, clip.full_range)
+    y, cb, cr = (torch.from_numpy(p).to(device) for p in (clip.y, clip.cb, clip.cr))
+    with E.device_guard(y):
+        out = ops.yuv420_to_clip_f32(y, cb, cr, coefs, chroma444=clip.colorspace == "C444")
+        return _pool_large(out).unsqueeze(0)
+
+
+def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs):
+    """(T,3,H,W) in [-1,1] -> uint8 planes Y (T,H,W), Cb, Cr (T,H/2,W/2) on the device: `postprocess_frames`' uint8 RGB value,
+    converted and 2x2-averaged in the same pass (reads the fp32 frames once, writes 1.5 bytes per pixel)."""
+    with E.device_guard(output):
+        return ops.clip_to_yuv420_u8(output.float().contiguous(), coefs)
+
+
+# ------------------------------------------------------------------------------------------------
+# YUV4MPEG2
+def read_y4m(path) -> Y4MClip:
+    """Read a progressive 8-bit YUV4MPEG2 file whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
+    (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is ignored: every 4:2:0 flavour is up-sampled by replicating
+    a sample over its 2x2 block.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
+    rest.  Anything else (4:2:2, mono, more than 8 bits, interlaced, a truncated frame) raises ValueError naming the tag."""
+    import numpy as np
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"\n")
+    if not data.startswith(b"YUV4MPEG2") or end < 0 or (end > 9 and data[9:10] != b" "):
+        raise ValueError(f"{path}: not a YUV4MPEG2 file (no 'YUV4MPEG2' signature line)")
+    w = h = None
+    fps, colorspace, full_range = None, "", None
+    for tag in data[10:end].decode("ascii", "replace").split():
+        key, val = tag[0], tag[1:]
+        try:
+            if key == "W":
+                w = int(val)
+            elif key == "H":
+                h = int(val)
+            elif key == "F":
+                num, den = (int(v) for v in val.split(":"))
+                fps = Fraction(num, den) if num > 0 and den > 0 else None
+        except ValueError:
+            raise ValueError(f"{path}: malformed header tag {tag!r}") from None
+        if key == "I" and val not in ("p", "?"):
+            raise ValueError(f"{path}: interlaced material is not supported (tag {tag!r})")
+        if key == "C":
+            if tag not in _CHROMA_420 + ("C444",):
+                raise ValueError(f"{path}: unsupported colour space {tag!r} (8-bit 4:2:0 and 4:4:4 only)")
+            colorspace = tag
+        if tag.startswith("XCOLORRANGE="):
+            if val[len("COLORRANGE="):] not in ("FULL", "LIMITED"):
+                raise ValueError(f"{path}: unsupported range tag {tag!r}")
+            full_range = val.endswith("=FULL")
+    if not w or not h or w < 0 or h < 0:
+        raise ValueError(f"{path}: the header has no valid W / H tags")
+    if full_range is None:
+        full_range = colorspace == "C420jpeg"
+    ch, cw = (h, w) if colorspace == "C444" else ((h + 1) // 2, (w + 1) // 2)
+    ysz, csz = h * w, ch * cw
+    pos, offsets = end + 1, []
+    while pos < len(data):
+        nl = data.find(b"\n", pos)
+        if not data.startswith(b"FRAME", pos) or nl < 0:
+            raise ValueError(f"{path}: 'FRAME' expected at byte {pos}")
+        pos = nl + 1                                                    # parameters on the FRAME line are skipped
+        if pos + ysz + 2 * csz > len(data):
+            raise ValueError(f"{path}: frame {len(offsets)} is truncated ('FRAME' with {len(data) - pos} of {ysz + 2 * csz} bytes)")
+        offsets.append(pos)
+        pos += ysz + 2 * csz
+    if not offsets:
+        raise ValueError(f"{path}: no 'FRAME' in the file")
+    buf = np.frombuffer(data, dtype=np.uint8)
+    y = np.stack([buf[o:o + ysz].reshape(h, w) for o in offsets])
+    cb = np.stack([buf[o + ysz:o + ysz + csz].reshape(ch, cw) for o in offsets])
+    cr = np.stack([buf[o + ysz + csz:o + ysz + 2 * csz].reshape(ch, cw) for o in offsets])
+    return Y4MClip(y, cb, cr, fps, (h, w), colorspace, full_range)
+
+
+def y4m_header(w: int, h: int, fps, full_range: bool) -> bytes:
+    fps = Fraction(str(fps)) if isinstance(fps, float) else Fraction(fps)
+    return (f"YUV4MPEG2 W{w} H{h} F{fps.numerator}:{fps.denominator} Ip A1:1 {'C420jpeg' if full_range else 'C420mpeg2'} "
+            f"XCOLORRANGE={'FULL' if full_range else 'LIMITED'}\n").encode("ascii")
+
+
+def write_y4m(path, y, cb, cr, fps, full_range: bool) -> None:
+    """Write 4:2:0 planes Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) (uint8 tensors on any device, or numpy arrays) as a
+    progressive YUV4MPEG2 file.  Device planes are gathered frame by frame on the device and cross to the host as ONE copy."""
+    import numpy as np
+    t, h, w = y.shape
+    cshape = (t, (h + 1) // 2, (w + 1) // 2)
+    if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
+        raise ValueError(f"write_y4m: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for 4:2:0")
+    if isinstance(y, torch.Tensor):
+        if not y.dtype == cb.dtype == cr.dtype == torch.uint8:
+            raise ValueError("write_y4m: uint8 planes expected")
+        frames = torch.cat([p.reshape(t, -1) for p in (y, cb, cr)], dim=1).cpu().numpy()           # (T, bytes of one frame)
+    else:
+        if not y.dtype == cb.dtype == cr.dtype == np.uint8:
+            raise ValueError("write_y4m: uint8 planes expected")
+        frames = np.concatenate([np.ascontiguousarray(p).reshape(t, -1) for p in (y, cb, cr)], axis=1)
+    with open(path, "wb") as fh:
+        fh.write(y4m_header(w, h, fps, full_range))
+        for i in range(t):
+            fh.write(b"FRAME\n")
+            fh.write(frames[i].tobytes())
+
+
+def read_frames(path):
+    """One video from `path`: a `.y4m` file -> (Y4MClip, fps); a `.npy` file of (T,H,W,3) uint8 RGB or a directory of images
+    (sorted names, decoded with PIL) -> ((T,H,W,3) uint8 numpy array, None)."""
+    import numpy as np
+    if os.path.isdir(path):
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith(IMAGE_EXTENSIONS))
+        if not names:
+            raise ValueError(f"{path}: no image files in the directory")
+        try:
+            from PIL import Image
+        except ImportError:
+            raise ValueError(f"{path}: reading image files needs the PIL package (Pillow)") from None
+        frames = [np.asarray(Image.open(os.path.join(path, n)).convert("RGB")) for n in names]
+        if len({f.shape for f in frames}) != 1:
+            raise ValueError(f"{path}: the images differ in size")
+        return np.stack(frames), None
+    low = str(path).lower()
+    if low.endswith(".y4m"):
+        clip = read_y4m(path)
+        return clip, clip.fps
+    if low.endswith(".npy"):
+        frames = np.load(path, allow_pickle=False)
+        if frames.ndim != 4 or frames.shape[-1] != 3 or frames.dtype != np.uint8:
+            raise ValueError(f"{path}: a (T,H,W,3) uint8 array expected, got {frames.dtype} {frames.shape}")
+        return frames, None
+    raise ValueError(f"{path}: unsupported input ('.y4m', '.npy' or a directory of images; convert other containers with "
+                     "`ffmpeg -i in.mp4 in.y4m`)")
+
+
+# ------------------------------------------------------------------------------------------------
+def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
+                 noise_level, tile_size=256, perform_tile=False, color_fix="None", generator) -> torch.Tensor:
+    """What the upscaling program does with one video between reading and writing it, in its order: bidirectional flows of
+    the whole clip when propagation steps are asked for, then either the tile loop (`tiling.needs_tiling`: asked for, or
+    h*w >= 384*384) or one pipeline call, then the optional colour fix against the bicubically up-sampled input.
+    `clip`: (1,3,T,h,w) in [-1,1] (preprocess_frames / preprocess_planes); returns the frames (T,3,4h,4w) fp32."""
+    from models_video import color_correction
+    from . import tiling
+    if color_fix not in ("None", "AdaIn", "Wavelet"):
+        raise ValueError(f"color_fix must be 'None', 'AdaIn' or 'Wavelet', got {color_fix!r}")
+    propagation_steps = list(propagation_steps)
+    if propagation_steps and raft is None:
+        raise ValueError("propagation steps need a flow estimator (raft=...)")
+    with torch.no_grad(), E.device_guard(clip):
+        flows_bi = list(raft.forward_slicing(clip)) if propagation_steps else None
+        h, w = clip.shape[-2:]
+        kwargs = dict(num_inference_steps=steps, guidance_scale=guidance_scale, noise_level=noise_level,
+                      negative_prompt=negative_prompt, propagation_steps=propagation_steps)
+        if tiling.needs_tiling(h, w, perform_tile):
+            output = tiling.upscale_tiled(pipeline, prompt, clip, flows_bi, generator, tile_size=tile_size, **kwargs)
+        else:
+            output = pipeline(prompt, image=clip, flows_bi=flows_bi, generator=generator, **kwargs).images
+        output = output.squeeze(0).permute(1, 0, 2, 3).contiguous()            # (T,3,4h,4w)
+        if color_fix != "None":
+            source = color_correction.upsample_bicubic4(clip.squeeze(0).permute(1, 0, 2, 3).contiguous())
+            fix = color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix
+            output = fix(output, source)
+        return output.float()
