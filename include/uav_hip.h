@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 7
+#define UAV_ABI_VERSION 8
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -529,6 +529,18 @@ int uav_yuv444_to_clip_f32(const void* y, const void* cb, const void* cr, float*
  * Cr likewise with fcr */
 int uav_clip_to_yuv420_u8(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
                           const int32_t* coefs, void* stream);
+/* the same conversion for a WINDOW of h x w pixels (both even, else UAV_ESHAPE) of t_len frames, read from and written into
+ * larger tensors without a copy.  `src` points at the window's first R value and is addressed in ELEMENTS: channel c, frame t,
+ * row r, pixel x at src[c*src_c_stride + t*src_t_stride + r*src_row_stride + x] — the decoder's (C,T,H,W) output, (T,C,H,W)
+ * frames, or any crop of either.  `y`, `cb`, `cr` point at the window's first sample inside their planes, addressed in BYTES:
+ * luma row r of frame t at y + t*y_frame + r*y_pitch, chroma row r at cb|cr + t*c_frame + r*c_pitch.  Strides must be >= 0 and
+ * the rows / frames of a plane must not overlap (y_pitch >= w, c_pitch >= w/2, frame strides past the last row when t_len > 1),
+ * else UAV_ESHAPE.  Bytes outside the window are not touched.  16-byte fp32 / 8- and 4-byte plane accesses are used when w, the
+ * pointers, the strides and the pitches allow them (e.g. a crop at a column offset that is a multiple of 4), scalar ones
+ * otherwise; the result does not depend on that. */
+int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride, void* y,
+                                 int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch, int64_t c_frame,
+                                 int32_t t_len, int32_t h, int32_t w, const int32_t* coefs, void* stream);
 
 #ifdef __cplusplus
 }

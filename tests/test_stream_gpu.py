@@ -1,0 +1,305 @@
+"""Streaming the 4x frames on the device: the window kernel (csrc/colorfix.hip `uav_clip_window_to_yuv420_u8`: a strided
+crop of decoder output converted straight into a box of larger planes) against tests/yuv_ref.py — bit for bit, with the bytes
+around the box and around the planes untouched —, its refusals, the program's files against the whole-clip path restated by
+hand (the colour fixes applied to the WHOLE clip there, per chunk in the program), and the peak of device memory."""
+import io
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, HERE)
+import yuv_ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GUARD = 4096
+
+
+def _values(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    out = torch.randn(shape, generator=g) * 0.8
+    flat = out.view(-1)
+    edge = torch.tensor([-1.0, 1.0, -1.5, 1.5, 0.0, 0.999999, -0.999999, 0.5])
+    flat[:min(8, flat.numel())] = edge[:min(8, flat.numel())]
+    return out
+
+
+class _Guarded:
+    """`nbytes` of device memory filled with 0xA5, with GUARD bytes of 0xA5 in front and behind (and `shift` bytes of misalignment)."""
+
+    def __init__(self, nbytes, dev, shift=0):
+        self.buf = torch.full((GUARD + shift + nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+        self.lo, self.n = GUARD + shift, nbytes
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.lo
+
+    def body(self):
+        return self.buf[self.lo:self.lo + self.n].cpu().numpy()
+
+    def intact(self):
+        return bool((self.buf[:self.lo] == 0xA5).all()) and bool((self.buf[self.lo + self.n:] == 0xA5).all())
+
+
+def _convert_window(dev, full, frames_first, box, plane_hw, at, shift, matrix, full_range):
+    """Window `box` = (y0, x0, h, w) of the tensor `full` ((3,T,H,W), or (T,3,H,W) with `frames_first`) through the C entry point
+    into planes of `plane_hw` at offset `at` = (row, column), and everything the test asks of the result."""
+    import ctypes
+    from uav import _lib, video_io
+    lib = _lib.load()
+    y0, x0, h, w = box
+    view = full[:, :, y0:y0 + h, x0:x0 + w]
+    c_dim, t_dim = (1, 0) if frames_first else (0, 1)
+    t = view.shape[t_dim]
+    ph, pw = plane_hw
+    oy, ox = at
+    planes = [_Guarded(t * ph * pw, dev, shift), _Guarded(t * ph * pw // 4, dev, shift), _Guarded(t * ph * pw // 4, dev, shift)]
+    fwd = (ctypes.c_int32 * 10)(*video_io.yuv_coefficients(matrix, full_range).forward)
+    src = view.data_ptr()
+    rc = lib.uav_clip_window_to_yuv420_u8(src, view.stride(c_dim), view.stride(t_dim), view.stride(2),
+                                          planes[0].ptr + oy * pw + ox, pw, ph * pw,
+                                          planes[1].ptr + (oy // 2) * (pw // 2) + ox // 2, planes[2].ptr + (oy // 2) * (pw // 2) + ox // 2,
+                                          pw // 2, ph * pw // 4, t, h, w, fwd, None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert all(p.intact() for p in planes), "a guard around the planes was written"
+    frames = (view if frames_first else view.permute(1, 0, 2, 3)).contiguous()                  # the materialised window (T,3,h,w)
+    ref = yuv_ref.encode(video_io.postprocess_frames(frames).cpu().numpy(), matrix, full_range)
+    for k, (p, r) in enumerate(zip(planes, ref)):
+        s = 1 if k == 0 else 2
+        got = p.body().reshape(t, ph // s, pw // s)
+        expect = np.full_like(got, 0xA5)
+        expect[:, oy // s:(oy + h) // s, ox // s:(ox + w) // s] = r
+        assert np.array_equal(got, expect), f"plane {k}: window or its surroundings differ"
+
+
+# (tensor H, W), window (y0, x0, h, w), planes (H, W), offset in the planes — and the access mode each one reaches
+WINDOWS = [((40, 56), (0, 0, 40, 56), (40, 56), (0, 0)),            # W % 8 == 0, whole tensor into whole planes: 16 / 8 / 4-byte accesses
+           ((12, 20), (0, 0, 12, 20), (12, 20), (0, 0)),            # W % 8 == 4: 4-byte luma, 2-byte chroma, a scalar 4-pixel tail
+           ((24, 48), (4, 4, 16, 40), (32, 64), (8, 16)),           # a crop at column 4 (fp32 rows stay 16-byte aligned) into a box
+           ((24, 48), (2, 4, 16, 36), (32, 72), (6, 12)),           # ... W % 8 == 4 and a box at column 12: the half-vector mode
+           ((24, 48), (2, 2, 8, 24), (32, 64), (8, 16)),            # a crop at column 2: misaligned fp32 rows, scalar
+           ((24, 48), (4, 4, 16, 40), (32, 62), (8, 10)),           # aligned source, odd pitches and an unaligned box
+           ((6, 8), (2, 4, 2, 2), (8, 12), (4, 6))]                 # a 2x2 window
+
+
+@pytest.mark.parametrize("matrix,full_range", yuv_ref.PAIRS)
+@pytest.mark.parametrize("frames_first", [False, True])
+@pytest.mark.parametrize("shape,box,plane_hw,at", WINDOWS)
+def test_window_kernel_equals_encoder_of_the_materialised_window(dev, shape, box, plane_hw, at, frames_first, matrix, full_range):
+    t = 3
+    full = _values((t, 3) + shape if frames_first else (3, t) + shape, seed=sum(shape) + sum(box)).to(dev)
+    _convert_window(dev, full, frames_first, box, plane_hw, at, 0, matrix, full_range)
+
+
+@pytest.mark.parametrize("shift", [1, 2])
+@pytest.mark.parametrize("shape,box,plane_hw,at", WINDOWS[:4] + WINDOWS[6:])
+def test_window_kernel_with_misaligned_plane_bases(dev, shape, box, plane_hw, at, shift):
+    full = _values((3, 2) + shape, seed=7 + shift).to(dev)
+    _convert_window(dev, full, False, box, plane_hw, at, shift, "bt709", False)
+
+
+@pytest.mark.parametrize("matrix,full_range", yuv_ref.PAIRS)
+def test_window_kernel_on_a_whole_decoder_chunk(dev, matrix, full_range):
+    """(1,3,3,1280,1280), the decoder's layout, whole: what the untiled program converts per chunk."""
+    full = _values((3, 3, 1280, 1280), seed=1280).to(dev)
+    _convert_window(dev, full, False, (0, 0, 1280, 1280), (1280, 1280), (0, 0), 0, matrix, full_range)
+
+
+def test_ops_wrapper_takes_views_and_copies_nothing(dev):
+    from uav import _lib, ops, video_io
+    coefs = video_io.yuv_coefficients("bt601", True)
+    dec = _values((1, 3, 3, 48, 64), seed=5).to(dev)                          # decoder output
+    planes = [torch.full((3, 96, 128), 0xA5, dtype=torch.uint8, device=dev)] + [torch.full((3, 48, 64), 0xA5, dtype=torch.uint8, device=dev)
+                                                                                  for _ in range(2)]
+    window = dec[0, :, :, 8:40, 4:60]                                         # (3,3,32,56), a tile's crop
+    boxes = [planes[0][:, 16:48, 32:88], planes[1][:, 8:24, 16:44], planes[2][:, 8:24, 16:44]]
+    assert ops.clip_window_to_yuv420_u8(window, *boxes, coefs) is None
+    ref = video_io.postprocess_planes(window.permute(1, 0, 2, 3).contiguous(), coefs)
+    for plane, box, r in zip(planes, boxes, ref):
+        assert torch.equal(box, r)
+        mask = torch.ones_like(plane, dtype=torch.bool)
+        if plane is planes[0]:
+            mask[:, 16:48, 32:88] = False
+        else:
+            mask[:, 8:24, 16:44] = False
+        assert bool((plane[mask] == 0xA5).all())
+    # (T,3,h,w) frames through the same entry point
+    frames = window.permute(1, 0, 2, 3)
+    again = [torch.empty_like(r) for r in ref]
+    ops.clip_window_to_yuv420_u8(frames, *again, coefs, frames_first=True)
+    assert all(torch.equal(a, r) for a, r in zip(again, ref))
+    for bad in ((window[..., ::2], boxes), (window.double(), boxes), (window.cpu(), boxes), (window[:, :, :31], boxes),
+                (window, [boxes[0], boxes[1], boxes[2][:, :, ::1].float()]), (window, [boxes[0][..., ::2]] + boxes[1:])):
+        with pytest.raises(_lib.UavError):
+            ops.clip_window_to_yuv420_u8(bad[0], *bad[1], coefs)
+
+
+def test_window_kernel_refuses_bad_arguments_before_any_launch(dev):
+    import ctypes
+    from uav import _lib, video_io
+    lib = _lib.load()
+    fwd = (ctypes.c_int32 * 10)(*video_io.yuv_coefficients("bt601", True).forward)
+    src = torch.zeros(3, 1, 6, 6, device=dev)
+    planes = [torch.full((64,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(3)]
+    p = [t.data_ptr() for t in planes]
+
+    def call(h, w, t_len=1, ptrs=None, coefs=fwd, strides=(36, 36, 6), pitches=(6, 36, 3, 9)):
+        s, y, cb, cr = ptrs or [src.data_ptr()] + p
+        return lib.uav_clip_window_to_yuv420_u8(s, *strides, y, pitches[0], pitches[1], cb, cr, pitches[2], pitches[3], t_len, h, w, coefs, None)
+    assert call(6, 6) == 0                                                    # the arguments the refusals below vary
+    torch.cuda.synchronize()
+    for t in planes:
+        t.fill_(0xA5)
+    for h, w in ((3, 6), (6, 5), (1, 1), (0, 6), (6, 0)):                       # odd or empty window
+        assert call(h, w) == -3                                               # UAV_ESHAPE
+    assert call(6, 6, t_len=0) == -3 and call(2, 2, t_len=70000) == -3
+    assert call(6, 6, strides=(36, 36, -6)) == -3
+    assert call(6, 6, pitches=(4, 36, 3, 9)) == -3 and call(6, 6, pitches=(6, 36, 2, 9)) == -3          # rows of a plane would overlap
+    assert call(6, 6, t_len=2, pitches=(6, 30, 3, 9)) == -3 and call(6, 6, t_len=2, pitches=(6, 36, 3, 8)) == -3   # ... or its frames
+    for hole in range(4):                                                      # null pointers
+        ptrs = [src.data_ptr()] + p
+        ptrs[hole] = None
+        assert call(6, 6, ptrs=ptrs) == -1                                    # UAV_EINVAL
+    assert call(6, 6, coefs=None) == -1
+    torch.cuda.synchronize()
+    assert all(bool((t == 0xA5).all()) for t in planes)                       # nothing was launched
+
+
+def test_program_and_memory_on_the_device(dev, tmp_path):
+    """10, 11 in one fresh process on the tiny seeded checkpoints (see `_child`).
+
+    11, measured on an MI355X (profiles/stream_output_path.txt), B = 28 311 552 bytes = one fp32 copy of the 24 added frames:
+      whole-clip path on the parent commit:  peak 521 501 696 (T = 12) -> 582 766 592 (T = 36), growth 61 264 896 = 2.164 B;
+      streamed path of this tree:            peak 511 179 776 (T = 12) -> 532 020 224 (T = 36), growth 20 840 448 = 0.736 B
+    (asserted: <= 61 264 896 - B = 32 953 344).  The streamed peak lies in the DDIM loop; what remains per frame is
+    20 840 448 / 24 = 868 352 bytes at 64x96 = 141 bytes per input pixel and frame.  This file adds 16 s to the GPU suite."""
+    r = subprocess.run([sys.executable, "-X", "faulthandler", os.path.abspath(__file__), str(tmp_path)], capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, f"exit status {r.returncode}:\n{r.stdout[-3000:]}\n{r.stderr[-6000:]}"
+    print(r.stdout[-3000:])
+
+
+# ---- child ---------------------------------------------------------------------------------------------------------------
+# Growth of the peak of device memory from T = 12 to T = 36 (64x96 input, 2 steps, tiny checkpoints) of the whole-clip path
+# `upscale_clip` -> `postprocess_planes` -> `write_y4m`, measured on an MI355X on the parent commit 4e1f3e2 (the last one whose
+# program held the whole clip): `python tools/mem_growth.py <built checkout of 4e1f3e2> hand out.json` (peaks 521 501 696 and
+# 582 766 592 bytes; record: profiles/stream_output_path.txt).
+G_PARENT = 61264896
+B = 24 * 3 * 256 * 384 * 4                                                      # one fp32 copy of the 24 added output frames
+
+
+def _whole_clip(pipe, clip, color_fix="None", raft=None, propagation_steps=(), perform_tile=False, tile_size=256):
+    """The whole-clip path the program had before it streamed, restated: one `pipeline(...)` / `upscale_tiled` call, the colour
+    fix on ALL frames at once, planes of all frames.  Returns the fp32 frames (T,3,4h,4w)."""
+    from models_video import color_correction
+    from uav import tiling
+    kw = dict(num_inference_steps=2, guidance_scale=6, noise_level=120, negative_prompt="blur, worst quality",
+              propagation_steps=list(propagation_steps))
+    gen = torch.Generator(device=clip.device).manual_seed(10)
+    prompt = "best quality, extremely detailed"
+    with torch.no_grad():
+        flows = list(raft.forward_slicing(clip)) if propagation_steps else None
+        if tiling.needs_tiling(*clip.shape[-2:], perform_tile):
+            out = tiling.upscale_tiled(pipe, prompt, clip, flows, gen, tile_size=tile_size, **kw)
+        else:
+            out = pipe(prompt, image=clip, flows_bi=flows, generator=gen, **kw).images
+        out = out.squeeze(0).permute(1, 0, 2, 3).contiguous()
+        if color_fix != "None":
+            source = color_correction.upsample_bicubic4(clip.squeeze(0).permute(1, 0, 2, 3).contiguous())
+            out = (color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix)(out, source)
+    return out.float()
+
+
+def _child(tmp):
+    import time
+    import synth
+    from test_cli_dropin_cpu import _clip_u8, _write_pretrained
+    from uav import cli, video_io
+    start = time.time()
+    dev = torch.device("cuda:0")
+    base = _write_pretrained(tmp)
+    os.chdir(tmp)
+
+    def write_input(name, t, h, w, seed):
+        rgb = _clip_u8(t, h, w, seed).permute(0, 2, 3, 1).contiguous().numpy()
+        video_io.write_y4m(name, *yuv_ref.encode(rgb, "bt601", True), "30000/1001", True)
+
+    write_input("fix7.y4m", 7, 64, 96, 51)
+    write_input("tiled4.y4m", 4, 68, 160, 52)
+    write_input("flow3.y4m", 3, 128, 160, 53)
+    jobs = (("fix7", ["--color_fix", "Wavelet"], dict(color_fix="Wavelet")),
+            ("tiled4", ["--color_fix", "AdaIn", "--perform_tile", "--tile_size", "64"], dict(color_fix="AdaIn", perform_tile=True, tile_size=64)),
+            ("tiled4", ["--perform_tile", "--tile_size", "64"], dict(perform_tile=True, tile_size=64)),
+            ("flow3", ["-p", "1"], dict(propagation_steps=[1])))
+    pipe, _ = cli.load_pipeline(base, device=dev)
+    # RAFT with seeded weights: `-p` reads propagator/raft-things.pth of the checkpoint directory
+    from models_video.RAFT.raft_bi import RAFT_bi
+    from models_video.propagation_module import Propagation
+    raft = RAFT_bi(model_path=None, device="cpu")
+    raft.fix_raft.load_state_dict(synth.synth_state_dict(raft.fix_raft.state_dict(), seed=777))
+    torch.save(raft.fix_raft.state_dict(), os.path.join(base, "propagator", "raft-things.pth"))
+    raft = raft.to(dev)
+    for k, (name, extra, kw) in enumerate(jobs):
+        argv = ["-i", name + ".y4m", "-s", "2", "--pretrained", base, "--device", "cuda:0"] + extra
+        assert cli.main(argv + ["-o", f"a{k}"]) == 0
+        assert cli.main(argv + ["-o", f"b{k}"]) == 0
+        prop = "_p1" if "-p" in extra else ""
+        out = f"a{k}/video/{name}_n120_g6_s2{prop}.y4m"
+        first = open(out, "rb").read()
+        assert first == open("b" + out[1:], "rb").read(), f"{name} {extra}: two runs of the program differ"
+        clip = video_io.preprocess_planes(video_io.read_y4m(name + ".y4m"), dev, "auto")
+        pipe.propagator = Propagation(4, learnable=False).to(dev) if prop else None
+        whole = _whole_clip(pipe, clip, raft=raft if prop else None, **kw)
+        coefs = video_io.yuv_coefficients(video_io.auto_matrix(whole.shape[-2]), True)
+        video_io.write_y4m("hand.y4m", *video_io.postprocess_planes(whole, coefs), "30000/1001", True)
+        assert first == open("hand.y4m", "rb").read(), f"{name} {extra}: the program's file != the whole-clip path"
+        assert video_io.read_y4m(out).y.std() > 5
+        print(f"{name} {' '.join(extra)}: {len(first)} bytes ok at {time.time() - start:.1f} s", flush=True)
+    pipe.propagator = None
+
+    # a colour fix per chunk == the fix on the whole clip (per-plane statistics, blur and resize), T = 7
+    clip = video_io.preprocess_planes(video_io.read_y4m("fix7.y4m"), dev, "auto")
+    opts = dict(prompt="best quality, extremely detailed", negative_prompt="blur, worst quality", steps=2, guidance_scale=6, noise_level=120)
+    for fix in ("AdaIn", "Wavelet"):
+        whole = _whole_clip(pipe, clip, color_fix=fix)
+        chunks = list(video_io.upscale_clip_chunks(pipe, clip, color_fix=fix, generator=torch.Generator(device=dev).manual_seed(10), **opts))
+        assert [len(c) for c in chunks] == [3, 3, 1] and torch.equal(torch.cat(chunks), whole), f"{fix}: per chunk != whole clip"
+        assert torch.equal(video_io.upscale_clip(pipe, clip, color_fix=fix, generator=torch.Generator(device=dev).manual_seed(10), **opts), whole)
+        assert not torch.equal(whole, _whole_clip(pipe, clip))
+    print(f"colour fixes per chunk ok at {time.time() - start:.1f} s", flush=True)
+
+    # 11. the peak of device memory: growth from T = 12 to T = 36
+    coefs = video_io.yuv_coefficients("bt601", True)
+
+    def streamed(t):
+        clip = synth.synth_clip(1, t, 64, 96, seed=60).to(dev)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        sink = io.BytesIO()
+        with video_io.Y4MWriter(sink, 384, 256, 24, True) as out:
+            for planes in video_io.upscale_clip_chunks(pipe, clip, coefs=coefs, generator=torch.Generator(device=dev).manual_seed(10), **opts):
+                out.write(*planes)
+        torch.cuda.synchronize()
+        assert out.frames == t
+        return torch.cuda.max_memory_allocated()
+    streamed(12)                                                               # warm-up: workspaces, caches
+    p12, p36 = streamed(12), streamed(36)
+    g = p36 - p12
+    print(f"memory: streamed peak T=12 {p12} B, T=36 {p36} B, growth {g} B = {g / B:.3f} B; parent growth {G_PARENT} B; "
+          f"B = {B} B; per added frame {g / 24:.0f} B at 64x96 = {g / 24 / (64 * 96):.1f} B per input pixel", flush=True)
+    assert g <= G_PARENT - B, f"streamed growth {g} B > parent growth {G_PARENT} B - B ({B} B)"
+    print(f"child total {time.time() - start:.1f} s", flush=True)
+
+
+if __name__ == "__main__":
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "upscale-a-video_amd")]
+    torch.set_num_threads(min(16, os.cpu_count() or 1))                         # as tests/conftest.py
+    _child(sys.argv[1])

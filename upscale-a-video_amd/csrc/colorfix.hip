@@ -320,6 +320,71 @@ __global__ __launch_bounds__(256) void yuv_to_clip_kernel(const unsigned char* _
         }
 }
 
+// The work of one thread of the two kernels below: `n` (even, <= YUV_RUN) pixels of two adjacent rows of one frame -> their luma
+// bytes and n/2 chroma samples.  `in`: the R value of the first pixel, G and B `cs` elements further each, the second row `rs`
+// elements further; `yd`: the first luma byte, the second row `yp` bytes further; `cbd` / `crd`: the first chroma sample.
+template <int MODE>
+UAV_DEVINL void clip_to_yuv420_run(const float* __restrict__ in, long long cs, long long rs, unsigned char* __restrict__ yd, long long yp,
+                                   unsigned char* __restrict__ cbd, unsigned char* __restrict__ crd, int n, const YuvFwd& k) {
+    if (MODE > 0 && n == YUV_RUN) {
+        int sr[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint32_t yw[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const float* p = in + r * rs + q * 4;
+                const float4_t R = *reinterpret_cast<const float4_t*>(p);
+                const float4_t G = *reinterpret_cast<const float4_t*>(p + cs);
+                const float4_t B = *reinterpret_cast<const float4_t*>(p + 2 * cs);
+                uint32_t word = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ir = yuv_clip_to_u8(R[j]), ig = yuv_clip_to_u8(G[j]), ib = yuv_clip_to_u8(B[j]);
+                    word |= (uint32_t)yuv_luma(k, ir, ig, ib) << (8 * j);
+                    sr[q * 2 + (j >> 1)] += ir; sg[q * 2 + (j >> 1)] += ig; sb[q * 2 + (j >> 1)] += ib;
+                }
+                yw[q] = word;
+            }
+            if (MODE == 2) {
+                uint2_t v; v.x = yw[0]; v.y = yw[1];
+                *reinterpret_cast<uint2_t*>(yd + r * yp) = v;
+            } else {
+                *reinterpret_cast<uint32_t*>(yd + r * yp) = yw[0];
+                *reinterpret_cast<uint32_t*>(yd + r * yp + 4) = yw[1];
+            }
+        }
+        uint32_t cbw = 0, crw = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            cbw |= (uint32_t)yuv_chroma(k.fcb, sr[c], sg[c], sb[c]) << (8 * c);
+            crw |= (uint32_t)yuv_chroma(k.fcr, sr[c], sg[c], sb[c]) << (8 * c);
+        }
+        if (MODE == 2) {
+            *reinterpret_cast<uint32_t*>(cbd) = cbw;
+            *reinterpret_cast<uint32_t*>(crd) = crw;
+        } else {
+            unsigned short* a = reinterpret_cast<unsigned short*>(cbd);
+            unsigned short* b = reinterpret_cast<unsigned short*>(crd);
+            a[0] = (unsigned short)cbw; a[1] = (unsigned short)(cbw >> 16);
+            b[0] = (unsigned short)crw; b[1] = (unsigned short)(crw >> 16);
+        }
+        return;
+    }
+    for (int c = 0; c < n / 2; ++c) {                                           // one 2x2 block at a time
+        int r4 = 0, g4 = 0, b4 = 0;
+        for (int r = 0; r < 2; ++r)
+            for (int j = 0; j < 2; ++j) {
+                const float* p = in + r * rs + c * 2 + j;
+                const int ir = yuv_clip_to_u8(p[0]), ig = yuv_clip_to_u8(p[cs]), ib = yuv_clip_to_u8(p[2 * cs]);
+                yd[r * yp + c * 2 + j] = (unsigned char)yuv_luma(k, ir, ig, ib);
+                r4 += ir; g4 += ig; b4 += ib;
+            }
+        cbd[c] = (unsigned char)yuv_chroma(k.fcb, r4, g4, b4);
+        crd[c] = (unsigned char)yuv_chroma(k.fcr, r4, g4, b4);
+    }
+}
+
 // frames (T,3,H,W) fp32 in [-1,1], H and W even -> planes Y (T,H,W), Cb / Cr (T,H/2,W/2)
 template <int MODE>
 __global__ __launch_bounds__(256) void clip_to_yuv420_kernel(const float* __restrict__ src, unsigned char* __restrict__ yp,
@@ -334,63 +399,26 @@ __global__ __launch_bounds__(256) void clip_to_yuv420_kernel(const float* __rest
     const float* in = src + (long long)t * 3 * hw + (long long)y0 * w + x0;    // channel stride: hw
     unsigned char* yd = yp + (long long)t * hw + (long long)y0 * w + x0;
     const long long co = ((long long)t * nry + ry) * cw + (x0 >> 1);
-    if (MODE > 0 && n == YUV_RUN) {
-        int sr[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            uint32_t yw[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float* p = in + (long long)r * w + q * 4;
-                const float4_t R = *reinterpret_cast<const float4_t*>(p);
-                const float4_t G = *reinterpret_cast<const float4_t*>(p + hw);
-                const float4_t B = *reinterpret_cast<const float4_t*>(p + 2 * hw);
-                uint32_t word = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ir = yuv_clip_to_u8(R[j]), ig = yuv_clip_to_u8(G[j]), ib = yuv_clip_to_u8(B[j]);
-                    word |= (uint32_t)yuv_luma(k, ir, ig, ib) << (8 * j);
-                    sr[q * 2 + (j >> 1)] += ir; sg[q * 2 + (j >> 1)] += ig; sb[q * 2 + (j >> 1)] += ib;
-                }
-                yw[q] = word;
-            }
-            if (MODE == 2) {
-                uint2_t v; v.x = yw[0]; v.y = yw[1];
-                *reinterpret_cast<uint2_t*>(yd + (long long)r * w) = v;
-            } else {
-                *reinterpret_cast<uint32_t*>(yd + (long long)r * w) = yw[0];
-                *reinterpret_cast<uint32_t*>(yd + (long long)r * w + 4) = yw[1];
-            }
-        }
-        uint32_t cbw = 0, crw = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            cbw |= (uint32_t)yuv_chroma(k.fcb, sr[c], sg[c], sb[c]) << (8 * c);
-            crw |= (uint32_t)yuv_chroma(k.fcr, sr[c], sg[c], sb[c]) << (8 * c);
-        }
-        if (MODE == 2) {
-            *reinterpret_cast<uint32_t*>(cbp + co) = cbw;
-            *reinterpret_cast<uint32_t*>(crp + co) = crw;
-        } else {
-            unsigned short* a = reinterpret_cast<unsigned short*>(cbp + co);
-            unsigned short* b = reinterpret_cast<unsigned short*>(crp + co);
-            a[0] = (unsigned short)cbw; a[1] = (unsigned short)(cbw >> 16);
-            b[0] = (unsigned short)crw; b[1] = (unsigned short)(crw >> 16);
-        }
-        return;
-    }
-    for (int c = 0; c < n / 2; ++c) {                                           // one 2x2 block at a time
-        int r4 = 0, g4 = 0, b4 = 0;
-        for (int r = 0; r < 2; ++r)
-            for (int j = 0; j < 2; ++j) {
-                const float* p = in + (long long)r * w + c * 2 + j;
-                const int ir = yuv_clip_to_u8(p[0]), ig = yuv_clip_to_u8(p[hw]), ib = yuv_clip_to_u8(p[2 * hw]);
-                yd[(long long)r * w + c * 2 + j] = (unsigned char)yuv_luma(k, ir, ig, ib);
-                r4 += ir; g4 += ig; b4 += ib;
-            }
-        cbp[co + c] = (unsigned char)yuv_chroma(k.fcb, r4, g4, b4);
-        crp[co + c] = (unsigned char)yuv_chroma(k.fcr, r4, g4, b4);
-    }
+    clip_to_yuv420_run<MODE>(in, hw, w, yd, w, cbp + co, crp + co, n, k);
+}
+
+// The same for a WINDOW of h x w pixels (both even) of t_len frames inside larger tensors: the source is addressed by element
+// strides of channel / frame / row (pixel stride 1: a crop of the decoder's (C,T,H,W) output, or of (T,C,H,W) frames), every
+// plane by its row pitch and frame stride in bytes, all pointers at the window's first sample.
+struct YuvWindow { long long sc, st, sr, yp, yf, cp, cf; };
+template <int MODE>
+__global__ __launch_bounds__(256) void clip_window_to_yuv420_kernel(const float* __restrict__ src, unsigned char* __restrict__ yp,
+                                                                    unsigned char* __restrict__ cbp, unsigned char* __restrict__ crp,
+                                                                    int h, int w, YuvWindow g, YuvFwd k) {
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = h / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int n = min(YUV_RUN, w - x0);                                         // even
+    const float* in = src + t * g.st + y0 * g.sr + x0;
+    unsigned char* yd = yp + t * g.yf + y0 * g.yp + x0;
+    const long long co = t * g.cf + ry * g.cp + (x0 >> 1);
+    clip_to_yuv420_run<MODE>(in, g.sc, g.sr, yd, g.yp, cbp + co, crp + co, n, k);
 }
 
 inline bool yuv_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -445,6 +473,34 @@ extern "C" int uav_clip_to_yuv420_u8(const float* frames_tchw, void* y, void* cb
     case 2: hipLaunchKernelGGL(clip_to_yuv420_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k); break;
     case 1: hipLaunchKernelGGL(clip_to_yuv420_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k); break;
     default: hipLaunchKernelGGL(clip_to_yuv420_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, frames_tchw, yp, cbp, crp, h, w, k);
+    }
+    return uav_launch_status();
+}
+
+extern "C" int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride,
+                                            void* y, int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch,
+                                            int64_t c_frame, int32_t t_len, int32_t h, int32_t w, const int32_t* coefs, void* stream) {
+    if (!src || !y || !cb || !cr || !coefs) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0 || (h & 1) || (w & 1)) return UAV_ESHAPE;
+    // no negative strides, and the rows / frames of a plane must not overlap (two threads would own one byte)
+    if (src_c_stride < 0 || src_t_stride < 0 || src_row_stride < 0 || y_pitch < w || c_pitch < w / 2) return UAV_ESHAPE;
+    if (t_len > 1 && (y_frame < (int64_t)(h - 1) * y_pitch + w || c_frame < (int64_t)(h / 2 - 1) * c_pitch + w / 2)) return UAV_ESHAPE;
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * (h / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    YuvFwd k;
+    for (int i = 0; i < 3; ++i) { k.fy[i] = coefs[i]; k.fcb[i] = coefs[3 + i]; k.fcr[i] = coefs[6 + i]; }
+    k.yo = coefs[9];
+    const YuvWindow g = {src_c_stride, src_t_stride, src_row_stride, y_pitch, y_frame, c_pitch, c_frame};
+    // the vector modes of yuv_mode() hold for every row of every frame only when the strides keep the alignment of the bases
+    int mode = (src_c_stride | src_t_stride | src_row_stride) % 4 == 0 ? yuv_mode(w, src, y, cb, cr, false) : 0;
+    if (mode == 2 && ((y_pitch | y_frame) % 8 != 0 || (c_pitch | c_frame) % 4 != 0)) mode = 1;      // what mode 2 asks implies mode 1
+    if (mode == 1 && ((y_pitch | y_frame) % 4 != 0 || (c_pitch | c_frame) % 2 != 0)) mode = 0;
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    unsigned char *yp = (unsigned char*)y, *cbp = (unsigned char*)cb, *crp = (unsigned char*)cr;
+    switch (mode) {
+    case 2: hipLaunchKernelGGL(clip_window_to_yuv420_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, src, yp, cbp, crp, h, w, g, k); break;
+    case 1: hipLaunchKernelGGL(clip_window_to_yuv420_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, yp, cbp, crp, h, w, g, k); break;
+    default: hipLaunchKernelGGL(clip_window_to_yuv420_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, yp, cbp, crp, h, w, g, k);
     }
     return uav_launch_status();
 }

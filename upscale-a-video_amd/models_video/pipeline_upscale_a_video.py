@@ -41,6 +41,18 @@ class StableDiffusionPipelineOutput(BaseOutput):
     nsfw_content_detected: Optional[List[bool]] = None
 
 
+@dataclass
+class Denoised:
+    """What `VideoUpscalePipeline.denoise` hands to the decode; its tensors live at the INPUT resolution.  `latents` (1,4,T,h,w)
+    in the loop's latent dtype, `image_dec` the fp32 low-resolution frames the VAE is conditioned on, `w_lr` its blend weight.
+    `overlap` is no data: the process-wide side-stream set the DDIM loop ran on (None = serial), kept so that `__call__` decodes
+    on the same streams; `decode_chunks` does not read it."""
+    latents: torch.Tensor
+    image_dec: torch.Tensor
+    w_lr: float = 1
+    overlap: object = None
+
+
 def randn_tensor(shape, generator=None, device=None, dtype=None):
     """diffusers.utils.randn_tensor: a CPU generator draws on the CPU, then the tensor moves."""
     rand_device = device
@@ -284,6 +296,14 @@ class VideoUpscalePipeline(ConfigMixin):
             return E.from_rows(y, g2, self.vae.config.out_channels, out_dtype=torch.float32, clamp=(-1.0, 1.0))
         return self.vae.decode(latents / sf, img, w_lr).sample.clamp(-1, 1).float()
 
+    def _device_ctx(self):
+        """Launches go to the current device's stream (uav/ops.py:_stream): the pipeline's GPU as the current device."""
+        device = self._execution_device
+        if device.type == "cuda" and device.index is not None and device.index != torch.cuda.current_device():
+            return torch.cuda.device(device)
+        import contextlib
+        return contextlib.nullcontext()
+
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, flows_bi: Optional[list] = None, num_inference_steps: int = 75,
@@ -291,6 +311,70 @@ class VideoUpscalePipeline(ConfigMixin):
                  negative_prompt=None, num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None,
                  latents=None, prompt_embeds=None, negative_prompt_embeds=None, propagation_steps: list = [],
                  w_lr: float = 1, return_dict: bool = True, progress: bool = False):
+        """`denoise`, then the whole clip decoded at once: the 3-frame chunks dealt over the ranks (`shard_windows`) or issued
+        on the side streams of the DDIM loop, and concatenated.  `decode_chunks` is the same decode one chunk at a time."""
+        den = self.denoise(prompt, image, flows_bi, num_inference_steps, guidance_scale, noise_level, denoise_level,
+                           negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
+                           negative_prompt_embeds, propagation_steps, w_lr)
+        with self._device_ctx():
+            latents, image_dec, overlap = den.latents, den.image_dec, den.overlap
+            device = self._execution_device
+            t_total, height, width = latents.shape[2:]
+            latents_out = latents.float()
+            # 11. decode in chunks of 3 frames on the GLOBAL frame index (:685-702)
+            short_seq = 3
+            if t_total > short_seq:
+                starts = list(range(0, t_total, short_seq))
+
+                def decode_chunk(s):
+                    e = min(t_total, s + short_seq)
+                    y = self._decode_chunk(den, s, e)
+                    if self.shard_windows and e - s < short_seq:      # ragged last chunk: pad to a common shape for the gather
+                        y = torch.cat([y, y.new_zeros(y.shape[:2] + (short_seq - (e - s),) + y.shape[3:])], dim=2)
+                    return y.contiguous()
+                like = ((1, image_dec.shape[1], short_seq, 4 * height, 4 * width), torch.float32, device)
+                if self.shard_windows:
+                    chunks = D.sharded_map(starts, decode_chunk, like=like)
+                else:
+                    chunks = overlap.map(starts, decode_chunk) if overlap is not None else [decode_chunk(s) for s in starts]
+                out = torch.cat(chunks, dim=2)[:, :, :t_total]
+            else:
+                out = self._decode_chunk(den, 0, t_total)
+        if not return_dict:
+            return (out, latents_out)
+        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+
+    def _decode_chunk(self, den, s, e):
+        """Frames [s, e) of a denoised clip -> (1,3,e-s,4h,4w) fp32 in [-1,1]; a clip of one chunk is decoded as it stands."""
+        if s == 0 and e == den.latents.shape[2]:
+            return self.decode_latents_vsr(den.latents, den.image_dec, den.w_lr)
+        return self.decode_latents_vsr(den.latents[:, :, s:e].contiguous(), den.image_dec[:, :, s:e].contiguous(), den.w_lr)
+
+    @torch.no_grad()
+    def decode_chunks(self, denoised: Denoised):
+        """Generator over the decode of a denoised clip: yields `(start, frames)` with `frames` (1,3,n,4h,4w) fp32 clamped to
+        [-1,1] for start = 0, 3, 6, ... (n <= 3; a clip of up to 3 frames is one chunk) — the chunk partition and the bits of
+        `__call__`, which are independent per chunk: the VAE decode draws no random numbers.  The generator holds no chunk
+        while it decodes the next one (a consumer that drops its own reference before `next()` has one chunk alive); all work
+        is on the caller's stream, and nothing runs between two `next()` calls.  Single process only."""
+        if self.shard_windows and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise ValueError("decode_chunks is single-process: with `shard_windows` and a process group, call the pipeline")
+        t_total = denoised.latents.shape[2]
+        for s in range(0, t_total, 3):
+            with self._device_ctx():                  # not held across the yield: the caller's current device is its own
+                y = self._decode_chunk(denoised, s, min(t_total, s + 3)).contiguous()
+            yield s, y
+            del y                                     # before the next chunk is decoded
+
+    @torch.no_grad()
+    def denoise(self, prompt=None, image=None, flows_bi: Optional[list] = None, num_inference_steps: int = 75,
+                guidance_scale: float = 9.0, noise_level: int = 20, denoise_level: Optional[int] = None,
+                negative_prompt=None, num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None,
+                latents=None, prompt_embeds=None, negative_prompt_embeds=None, propagation_steps: list = [],
+                w_lr: float = 1, return_dict: bool = True, progress: bool = False) -> Denoised:
+        """Everything of a call before the decode, with the arguments of `__call__`: input checks, prompt, both noise draws
+        (LR noise, then latents), the window schedule, the DDIM loop and propagation.  What it returns lives at the input
+        resolution; `decode_chunks` or `__call__` turn it into 4x frames."""
         self.check_inputs(prompt, image, noise_level, negative_prompt, prompt_embeds, negative_prompt_embeds)
         if image is None:
             raise ValueError("`image` input cannot be undefined.")
@@ -299,13 +383,14 @@ class VideoUpscalePipeline(ConfigMixin):
         batch_size = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else prompt_embeds.shape[0]
         if batch_size != 1 or num_images_per_prompt != 1:
             raise NotImplementedError("the CLI upscales one clip per call")
+        with self._device_ctx():
+            return self._denoise(prompt, image, flows_bi, num_inference_steps, guidance_scale, noise_level, denoise_level,
+                                 negative_prompt, num_images_per_prompt, generator, latents, prompt_embeds,
+                                 negative_prompt_embeds, propagation_steps, w_lr)
+
+    def _denoise(self, prompt, image, flows_bi, num_inference_steps, guidance_scale, noise_level, denoise_level, negative_prompt,
+                 num_images_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, propagation_steps, w_lr):
         device = self._execution_device
-        if device.type == "cuda" and device.index is not None and device.index != torch.cuda.current_device():
-            # launches go to the current device's stream (uav/ops.py:_stream): make the pipeline's GPU current
-            with torch.cuda.device(device):
-                return self.__call__(prompt, image, flows_bi, num_inference_steps, guidance_scale, noise_level, denoise_level,
-                                     negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
-                                     negative_prompt_embeds, propagation_steps, w_lr, return_dict, progress)
         do_cfg = guidance_scale > 1.0
 
         prompt_embeds = self._cached_prompt_embeds(prompt, device, num_images_per_prompt, do_cfg, negative_prompt,
@@ -332,6 +417,7 @@ class VideoUpscalePipeline(ConfigMixin):
         image = image.to(dtype=lat_dtype, device=device)
         noise = randn_tensor(image.shape, generator=generator, device=device, dtype=draw_dtype).to(lat_dtype)
         image = self.low_res_scheduler.add_noise(image, noise, torch.tensor([noise_level]))
+        del noise
         level = torch.tensor([noise_level if denoise_level is None else denoise_level], dtype=torch.long)
         # reference quirk kept: the single-window branch (T <= 8) conditions the UNet on `noise_level` even when a
         # `denoise_level` was passed (:638), only the sliding-window branch uses `denoise_level` (:628)
@@ -367,6 +453,10 @@ class VideoUpscalePipeline(ConfigMixin):
             flows_f = flows_bi[0].to(device=device, dtype=lat_dtype)
             flows_b = flows_bi[1].to(device=device, dtype=lat_dtype)
 
+        # What a clip holds PER FRAME limits its length (the 4x frames need not exist whole: `decode_chunks`), so every per-frame
+        # tensor of a step is dropped as soon as its last reader is issued rather than when the next step rebinds the name: the
+        # peak is one step's live set, not two steps' overlapped.  (Blocks of the side streams' pools are only reused by later
+        # units on the same stream, which wait for this stream first: uav/streams.py.)
         for i, t in enumerate(timesteps):
             lin = torch.cat([latents] * 2) if do_cfg else latents
             uniq = [w for k, w in enumerate(wins) if w not in wins[:k]]
@@ -390,6 +480,8 @@ class VideoUpscalePipeline(ConfigMixin):
             else:
                 res = overlap.map(units, eval_unit) if overlap is not None else [eval_unit(u) for u in units]
             outs = {w: (torch.cat([res[2 * k], res[2 * k + 1]]) if split else res[k]) for k, w in enumerate(uniq)}
+            del lin, res
+            o = None                                  # (bound by the blend loop below when there are several windows)
             if len(wins) > 1:
                 eps = None
                 written = [False] * t_total
@@ -406,39 +498,20 @@ class VideoUpscalePipeline(ConfigMixin):
             else:
                 eps = outs[wins[0]]
             eps = eps.contiguous()
+            del o, outs
             if do_cfg:
                 guided, x0 = self.scheduler.cfg_step_v0(eps[0:1], eps[1:2], guidance_scale, t, latents)
             else:
                 guided, x0 = self.scheduler.cfg_step_v0(eps, None, 1.0, t, latents)
+            del eps
             if flows_bi is not None and i in propagation_steps:
                 # fp16 latents: the kernel replays the reference's fp16 warp (bit-exact against it on half tensors);
                 # fp32 latents: fp32 values on fp32 grids, held to the reference's fp32 run (no rounding of the trajectory)
                 x0 = self.propagator(x0, flows_f, flows_b, interpolation="nearest", mode="fuse",
                                      fuse_scale=0.5, alpha1=0.001, alpha2=0.05).to(lat_dtype).contiguous()
             latents = self.scheduler.step_vt(x0, guided, t, latents).prev_sample
+            del guided, x0
             if self.latents_trace is not None:        # test hook: per-step latents (error-vs-step curves)
                 self.latents_trace.append(latents.clone())
 
-        latents_out = latents.float()
-        # 11. decode in chunks of 3 frames on the GLOBAL frame index (:685-702)
-        short_seq = 3
-        if t_total > short_seq:
-            starts = list(range(0, t_total, short_seq))
-
-            def decode_chunk(s):
-                e = min(t_total, s + short_seq)
-                y = self.decode_latents_vsr(latents[:, :, s:e].contiguous(), image_dec[:, :, s:e].contiguous(), w_lr)
-                if self.shard_windows and e - s < short_seq:      # ragged last chunk: pad to a common shape for the gather
-                    y = torch.cat([y, y.new_zeros(y.shape[:2] + (short_seq - (e - s),) + y.shape[3:])], dim=2)
-                return y.contiguous()
-            like = ((1, image_dec.shape[1], short_seq, 4 * height, 4 * width), torch.float32, device)
-            if self.shard_windows:
-                chunks = D.sharded_map(starts, decode_chunk, like=like)
-            else:
-                chunks = overlap.map(starts, decode_chunk) if overlap is not None else [decode_chunk(s) for s in starts]
-            out = torch.cat(chunks, dim=2)[:, :, :t_total]
-        else:
-            out = self.decode_latents_vsr(latents, image_dec, w_lr)
-        if not return_dict:
-            return (out, latents_out)
-        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+        return Denoised(latents=latents, image_dec=image_dec, w_lr=w_lr, overlap=overlap)

@@ -4,9 +4,14 @@
     python upscale.py -i in.y4m -o results --pretrained pretrained_models/upscale_a_video
     ffmpeg -i results/video/in_n120_g6_s30.y4m out.mp4
 
+or, with no file in between (`-i -` reads one Y4M stream from standard input, `--y4m-out -` writes it to standard output):
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python upscale.py -i - --y4m-out - --pretrained DIR | ffmpeg -i - out.mp4
+
 (`python -m uav.cli` with `upscale-a-video_amd` on the path is the same program.)  It takes the options of the reference
-project's `inference_upscale_a_video.py` and does per video what that program does — `video_io.upscale_clip` — but reads
-and writes by itself: YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and
+project's `inference_upscale_a_video.py` and does per video what that program does — `video_io.upscale_clip_chunks` — 3 output
+frames at a time: the input is read whole (the DDIM loop needs all of it, at 1/16 of the output's size), the 4x frames go to
+the file chunk by chunk and never exist as one clip.  It reads and writes by itself: YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and
 directories of images in; `.y4m` (4:2:0) out, the colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`,
 `uav_clip_to_yuv420_u8`).  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
 each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
@@ -45,7 +50,8 @@ def _fps(text):
 
 def build_parser():
     p = argparse.ArgumentParser(prog="upscale.py", description="Upscale-A-Video on an MI355X: 4x video super-resolution, Y4M in and out.")
-    p.add_argument("-i", "--input_path", required=True, help="a .y4m / .npy file, a directory of images, or a directory of those")
+    p.add_argument("-i", "--input_path", required=True,
+                   help="a .y4m / .npy file, a directory of images, a directory of those, or - for one Y4M stream on standard input")
     p.add_argument("-o", "--output_path", default="./results", help="output folder (videos go to <out>/video)")
     p.add_argument("--pretrained", required=True, metavar="DIR", help="released checkpoint directory (pretrained_models/upscale_a_video)")
     p.add_argument("-n", "--noise_level", type=int, default=120, help="noise level [0, 200] applied to the input video")
@@ -59,6 +65,8 @@ def build_parser():
     p.add_argument("--color_fix", default="None", choices=["None", "AdaIn", "Wavelet"])
     p.add_argument("--perform_tile", action="store_true")
     p.add_argument("--tile_size", type=int, default=256)
+    p.add_argument("--y4m-out", dest="y4m_out", metavar="FILE|-", default=None,
+                   help="write the one output video to FILE, or to standard output with - (the per-video line then goes to standard error)")
     p.add_argument("--save_image", action="store_true", help="also write PNG frames to <out>/frame/<name> (needs PIL)")
     p.add_argument("--save_suffix", default="")
     p.add_argument("--matrix", default="auto", choices=["auto", "bt601", "bt709"],
@@ -129,19 +137,22 @@ def list_videos(path):
     return videos
 
 
-def _save_png(frames_u8, folder):
+def _save_png(frames_u8, folder, first=0):
     try:
         from PIL import Image
     except ImportError:
         raise UserError("--save_image needs the PIL package (Pillow)") from None
     os.makedirs(folder, exist_ok=True)
-    for i, frame in enumerate(frames_u8):
+    for i, frame in enumerate(frames_u8, first):
         Image.fromarray(frame).save(os.path.join(folder, f"{i:04d}.png"))
 
 
 def _read(path):
     from . import video_io
     try:
+        if path == "-":
+            clip = video_io.read_y4m(sys.stdin.buffer)
+            return clip, clip.fps
         return video_io.read_frames(path)
     except (ValueError, OSError) as e:
         raise UserError(str(e)) from None
@@ -149,7 +160,9 @@ def _read(path):
 
 def run(args):
     from . import tiling, video_io
-    videos = list_videos(args.input_path)
+    videos = ["-"] if args.input_path == "-" else list_videos(args.input_path)
+    if args.y4m_out is not None and len(videos) > 1:
+        raise UserError(f"--y4m-out takes one video, {args.input_path} holds {len(videos)}")
     device = torch.device(args.device)
     if device.type == "cuda" and not torch.cuda.is_available():
         raise UserError(f"--device {args.device}: no GPU is visible")
@@ -161,7 +174,7 @@ def run(args):
     for index, path in enumerate(videos):
         source, fps = first if index == 0 else _read(path)
         first = None
-        name = os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
+        name = "stdin" if path == "-" else os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
         if isinstance(source, video_io.Y4MClip):
             clip = video_io.preprocess_planes(source, device, args.matrix)
             in_size = source.size
@@ -172,35 +185,46 @@ def run(args):
         t, (h, w) = clip.shape[2], clip.shape[-2:]
         tiles = len(tiling.tile_grid(h, w, args.tile_size)) if tiling.needs_tiling(h, w, args.perform_tile) else 1
         generator = torch.Generator(device=device).manual_seed(args.seed)
-        if device.type == "cuda":
-            torch.cuda.synchronize(device)
-        start = time.time()
-        output = video_io.upscale_clip(pipeline, clip, prompt=prompt, negative_prompt=args.n_prompt, raft=raft,
-                                       propagation_steps=args.propagation_steps, steps=args.inference_steps,
-                                       guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
-                                       perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator)
         full_range = source.full_range if isinstance(source, video_io.Y4MClip) else True
-        matrix = video_io.auto_matrix(output.shape[-2]) if args.matrix == "auto" else args.matrix
-        y, cb, cr = video_io.postprocess_planes(output, video_io.yuv_coefficients(matrix, full_range))
-        if device.type == "cuda":
-            torch.cuda.synchronize(device)
-        seconds = time.time() - start
+        coefs = video_io.yuv_coefficients(video_io.auto_matrix(4 * h) if args.matrix == "auto" else args.matrix, full_range)
         prop = "_p" + "_".join(map(str, args.propagation_steps)) if args.propagation_steps else ""
         suffix = "_" + args.save_suffix if args.save_suffix else ""
         save_name = f"{name}_n{args.noise_level}_g{args.guidance_scale}_s{args.inference_steps}{prop}{suffix}"
-        os.makedirs(os.path.join(args.output_path, "video"), exist_ok=True)
-        out_path = os.path.join(args.output_path, "video", save_name + ".y4m")
-        video_io.write_y4m(out_path, y, cb, cr, args.fps or fps or 24, full_range)
-        if args.save_image or (args.dump_rgb and index == len(videos) - 1):
-            rgb = video_io.postprocess_frames(output).cpu().numpy()
-            if args.save_image:
-                _save_png(rgb, os.path.join(args.output_path, "frame", save_name))
-            if args.dump_rgb and index == len(videos) - 1:
-                import numpy as np
-                with open(args.dump_rgb, "wb") as fh:
-                    np.save(fh, rgb)
+        if args.y4m_out is None:
+            os.makedirs(os.path.join(args.output_path, "video"), exist_ok=True)
+            out_path = os.path.join(args.output_path, "video", save_name + ".y4m")
+        else:
+            out_path = args.y4m_out
+        dump = [] if args.dump_rgb and index == len(videos) - 1 else None
+        need_frames = args.save_image or dump is not None       # the uint8 RGB frames are made from the fp32 chunk, like the planes
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        start = time.time()
+        chunks = video_io.upscale_clip_chunks(pipeline, clip, prompt=prompt, negative_prompt=args.n_prompt, raft=raft,
+                                              propagation_steps=args.propagation_steps, steps=args.inference_steps,
+                                              guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
+                                              perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
+                                              coefs=None if need_frames else coefs)
+        with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, 4 * w, 4 * h, args.fps or fps or 24, full_range) as out:
+            for chunk in chunks:                                # one chunk is alive: decoded, converted and written before the next
+                if need_frames:
+                    rgb = video_io.postprocess_frames(chunk).cpu().numpy()
+                    if args.save_image:
+                        _save_png(rgb, os.path.join(args.output_path, "frame", save_name), first=out.frames)
+                    if dump is not None:
+                        dump.append(rgb)
+                    chunk = video_io.postprocess_planes(chunk, coefs)
+                out.write(*chunk)
+                del chunk                                       # before the generator decodes the next one
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        seconds = time.time() - start
+        if dump is not None:
+            import numpy as np
+            with open(args.dump_rgb, "wb") as fh:
+                np.save(fh, np.concatenate(dump))
         print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {4 * h}x{4 * w}, {tiles} tile(s), "
-              f"{seconds:.2f} s -> {out_path}", flush=True)
+              f"{seconds:.2f} s -> {out_path}", file=sys.stderr if out_path == "-" else sys.stdout, flush=True)
     return out_path
 
 

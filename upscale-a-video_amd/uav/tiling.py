@@ -12,7 +12,12 @@ a list of `Tile` records, and `upscale_tiled` runs them
     573`) and the result is bit-identical to the serial loop.  The disjoint output boxes are merged by one all-reduce
     of the output canvas (adding zeros is exact).
 
-Only index arithmetic and scheduling live here; the per-tile work is `VideoUpscalePipeline.__call__`.
+`upscale_tiled_chunks` is the single-process loop in two phases, for a clip whose 4x result should never exist whole: every
+tile is denoised first (`pipeline.denoise`, same order, same shared generator: all random draws happen there), then the clip
+is decoded 3 frames at a time, every tile's share of a chunk going to the caller before the next chunk is touched.
+
+Only index arithmetic and scheduling live here; the per-tile work is `VideoUpscalePipeline.__call__` / `denoise` +
+`decode_chunks`.
 """
 import math
 from dataclasses import dataclass
@@ -120,3 +125,33 @@ def upscale_tiled(pipeline, prompt, vframes: torch.Tensor, flows_bi: Optional[li
         else:
             dist.all_reduce(out, op=dist.ReduceOp.SUM, group=group)           # disjoint boxes: x + 0 is exact
     return out
+
+
+def upscale_tiled_chunks(pipeline, prompt, vframes: torch.Tensor, flows_bi: Optional[list], generator: torch.Generator, *,
+                         tile_size: int = 256, **pipeline_kwargs):
+    """`upscale_tiled` for one process, 3 frames at a time.  Generator of `(start, n, pieces)` for start = 0, 3, 6, ...:
+    `pieces` is itself a generator of `(dst, crop)`, one per tile in `tile_grid` order — `crop` the (C,n,dy,dx) view of that
+    tile's decoded frames [start, start+n) that belongs into the box `dst` = (y0, y1, x0, x1) of the 4x frames (boxes are
+    disjoint, cover the frame and start on multiples of 4).  Drain `pieces` before asking for the next chunk.  Assembled,
+    the pieces are `upscale_tiled`'s result bit for bit; what is held between chunks is per tile the `Denoised` record, at the
+    input resolution."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError("upscale_tiled_chunks is single-process; `upscale_tiled` deals the tiles over the ranks of a process group")
+    t, h, w = vframes.shape[2:]
+    tiles = tile_grid(h, w, tile_size)
+    denoised = []
+    for tl in tiles:                                                           # phase 1: the serial loop's calls up to the decode
+        y0, y1, x0, x1 = tl.src
+        tile_flows = None if flows_bi is None else [f[:, :, :, y0:y1, x0:x1] for f in flows_bi]
+        denoised.append(pipeline.denoise(prompt, image=vframes[:, :, :, y0:y1, x0:x1], flows_bi=tile_flows, generator=generator,
+                                         **pipeline_kwargs))
+
+    def pieces(decoders):
+        for tl, dec in zip(tiles, decoders):
+            _, frames = next(dec)
+            cy0, cy1, cx0, cx1 = tl.crop
+            yield tl.dst, frames[0, :, :, cy0:cy1, cx0:cx1]
+
+    decoders = [pipeline.decode_chunks(d) for d in denoised]                   # phase 2: every tile advances one chunk at a time
+    for start in range(0, t, 3):
+        yield start, min(3, t - start), pieces(decoders)

@@ -105,13 +105,17 @@ def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs):
 # ------------------------------------------------------------------------------------------------
 # YUV4MPEG2
 def read_y4m(path) -> Y4MClip:
-    """Read a progressive 8-bit YUV4MPEG2 file whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
+    """Read a progressive 8-bit YUV4MPEG2 file — `path`, or an open binary stream such as a pipe, named by its `.name` in
+    messages — whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
     (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is ignored: every 4:2:0 flavour is up-sampled by replicating
     a sample over its 2x2 block.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
     rest.  Anything else (4:2:2, mono, more than 8 bits, interlaced, a truncated frame) raises ValueError naming the tag."""
     import numpy as np
-    with open(path, "rb") as fh:
-        data = fh.read()
+    if hasattr(path, "read"):
+        data, path = path.read(), getattr(path, "name", "<stream>")
+    else:
+        with open(path, "rb") as fh:
+            data = fh.read()
     end = data.find(b"\n")
     if not data.startswith(b"YUV4MPEG2") or end < 0 or (end > 9 and data[9:10] != b" "):
         raise ValueError(f"{path}: not a YUV4MPEG2 file (no 'YUV4MPEG2' signature line)")
@@ -170,27 +174,76 @@ def y4m_header(w: int, h: int, fps, full_range: bool) -> bytes:
             f"XCOLORRANGE={'FULL' if full_range else 'LIMITED'}\n").encode("ascii")
 
 
+class Y4MWriter:
+    """A progressive 4:2:0 YUV4MPEG2 stream written chunk by chunk: the header once, then `write(y, cb, cr)` appends the frames
+    of planes Y (n,H,W), Cb, Cr (n,ceil(H/2),ceil(W/2)) — uint8 tensors on any device, or numpy arrays.  Device planes are
+    gathered frame by frame on the device and cross to the host as ONE copy per call.  `path_or_file`: an open binary stream
+    (a pipe will do: nothing seeks), or a path — then the bytes go to `<path>.part`, which takes the name only on a clean exit:
+    a Y4M file has no frame count, so a file cut short by a failure would look complete."""
+
+    def __init__(self, path_or_file, w: int, h: int, fps, full_range: bool):
+        self.w, self.h, self.frames = int(w), int(h), 0
+        self._path = None if hasattr(path_or_file, "write") else os.fspath(path_or_file)
+        self._fh = path_or_file if self._path is None else open(self._path + ".part", "wb")
+        try:
+            self._fh.write(y4m_header(self.w, self.h, fps, full_range))
+        except BaseException:
+            self.close(False)
+            raise
+
+    def write(self, y, cb, cr) -> None:
+        import numpy as np
+        if len(y.shape) != 3 or tuple(y.shape[1:]) != (self.h, self.w):
+            raise ValueError(f"Y4MWriter: luma planes {tuple(y.shape)}, expected (n, {self.h}, {self.w})")
+        t = y.shape[0]
+        cshape = (t, (self.h + 1) // 2, (self.w + 1) // 2)
+        if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
+            raise ValueError(f"Y4MWriter: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for 4:2:0")
+        if isinstance(y, torch.Tensor):
+            if not y.dtype == cb.dtype == cr.dtype == torch.uint8:
+                raise ValueError("Y4MWriter: uint8 planes expected")
+            frames = torch.cat([p.reshape(t, -1) for p in (y, cb, cr)], dim=1).cpu().numpy()       # (n, bytes of one frame)
+        else:
+            if not y.dtype == cb.dtype == cr.dtype == np.uint8:
+                raise ValueError("Y4MWriter: uint8 planes expected")
+            frames = np.concatenate([np.ascontiguousarray(p).reshape(t, -1) for p in (y, cb, cr)], axis=1)
+        for i in range(t):
+            self._fh.write(b"FRAME\n")
+            self._fh.write(frames[i].tobytes())
+        self._fh.flush()                                  # a reader on the other end of a pipe gets every chunk as it is made
+        self.frames += t
+
+    def close(self, complete: bool = True) -> None:
+        """Flush; a file opened by path is closed and, when `complete`, renamed from `<path>.part` (else removed)."""
+        fh, self._fh = self._fh, None
+        if fh is None:
+            return
+        if self._path is None:
+            fh.flush()
+            return
+        fh.close()
+        if complete:
+            os.replace(self._path + ".part", self._path)
+        else:
+            os.remove(self._path + ".part")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(exc_type is None)
+        return False
+
+
 def write_y4m(path, y, cb, cr, fps, full_range: bool) -> None:
     """Write 4:2:0 planes Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) (uint8 tensors on any device, or numpy arrays) as a
-    progressive YUV4MPEG2 file.  Device planes are gathered frame by frame on the device and cross to the host as ONE copy."""
-    import numpy as np
+    progressive YUV4MPEG2 file: one `Y4MWriter.write`."""
     t, h, w = y.shape
     cshape = (t, (h + 1) // 2, (w + 1) // 2)
     if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
         raise ValueError(f"write_y4m: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for 4:2:0")
-    if isinstance(y, torch.Tensor):
-        if not y.dtype == cb.dtype == cr.dtype == torch.uint8:
-            raise ValueError("write_y4m: uint8 planes expected")
-        frames = torch.cat([p.reshape(t, -1) for p in (y, cb, cr)], dim=1).cpu().numpy()           # (T, bytes of one frame)
-    else:
-        if not y.dtype == cb.dtype == cr.dtype == np.uint8:
-            raise ValueError("write_y4m: uint8 planes expected")
-        frames = np.concatenate([np.ascontiguousarray(p).reshape(t, -1) for p in (y, cb, cr)], axis=1)
-    with open(path, "wb") as fh:
-        fh.write(y4m_header(w, h, fps, full_range))
-        for i in range(t):
-            fh.write(b"FRAME\n")
-            fh.write(frames[i].tobytes())
+    with Y4MWriter(path, w, h, fps, full_range) as out:
+        out.write(y, cb, cr)
 
 
 def read_frames(path):
@@ -223,12 +276,32 @@ def read_frames(path):
 
 
 # ------------------------------------------------------------------------------------------------
-def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
-                 noise_level, tile_size=256, perform_tile=False, color_fix="None", generator) -> torch.Tensor:
-    """What the upscaling program does with one video between reading and writing it, in its order: bidirectional flows of
-    the whole clip when propagation steps are asked for, then either the tile loop (`tiling.needs_tiling`: asked for, or
-    h*w >= 384*384) or one pipeline call, then the optional colour fix against the bicubically up-sampled input.
-    `clip`: (1,3,T,h,w) in [-1,1] (preprocess_frames / preprocess_planes); returns the frames (T,3,4h,4w) fp32."""
+def _window_to_planes(window, planes, dst, coefs):
+    """One piece of a chunk — `window` (3,n,dy,dx), a view of decoder output — converted into the box `dst` = (y0, y1, x0, x1)
+    of the chunk's planes Y (n,H,W), Cb, Cr (n,H/2,W/2).  On the device this is ONE kernel that reads the view in place and
+    writes the box (`ops.clip_window_to_yuv420_u8`).  The only place that decides about host tensors: `uav.ops` has no CPU
+    path — every op raises `UavError` for a host tensor, and so does this one in production — but the CPU tests swap
+    `ops.clip_to_yuv420_u8` for a torch stand-in (tests/cpu_ops_io.py) and know nothing of newer symbols, so a host window
+    goes through that entry point on a contiguous copy and is placed with torch indexing."""
+    y0, y1, x0, x1 = dst
+    boxes = [p[:, a:b, c:d] for p, (a, b, c, d) in zip(planes, ((y0, y1, x0, x1),) + ((y0 // 2, y1 // 2, x0 // 2, x1 // 2),) * 2)]
+    if window.is_cuda:
+        ops.clip_window_to_yuv420_u8(window, *boxes, coefs)
+    else:
+        for box, plane in zip(boxes, ops.clip_to_yuv420_u8(window.permute(1, 0, 2, 3).contiguous(), coefs)):
+            box.copy_(plane)
+
+
+def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
+                        noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None):
+    """What the upscaling program does with one video between reading and writing it, in its order, 3 output frames at a time:
+    bidirectional flows of the whole clip when propagation steps are asked for, then the DDIM loop of the whole clip — of
+    every tile (`tiling.needs_tiling`: asked for, or h*w >= 384*384), or of the one pipeline call — whose results live at the
+    input resolution, then per chunk the decode and the optional colour fix against the bicubically up-sampled input frames
+    of that chunk (statistics, blur and resize are per frame).  `clip`: (1,3,T,h,w) in [-1,1] (preprocess_frames /
+    preprocess_planes).  A generator of the chunks' frames (n,3,4h,4w) fp32, n <= 3 — or, with `coefs`, of their 4:2:0 planes
+    (y, cb, cr) as `postprocess_planes` returns them; without a colour fix those are converted straight from the decoder's
+    output, tile by tile, and no fp32 frame of the 4x clip is assembled at all."""
     from models_video import color_correction
     from . import tiling
     if color_fix not in ("None", "AdaIn", "Wavelet"):
@@ -236,18 +309,43 @@ def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=
     propagation_steps = list(propagation_steps)
     if propagation_steps and raft is None:
         raise ValueError("propagation steps need a flow estimator (raft=...)")
-    with torch.no_grad(), E.device_guard(clip):
+    h, w = clip.shape[-2:]
+    kwargs = dict(num_inference_steps=steps, guidance_scale=guidance_scale, noise_level=noise_level,
+                  negative_prompt=negative_prompt, propagation_steps=propagation_steps)
+    with torch.no_grad(), E.device_guard(clip):          # (no guard is held across a `yield`: the caller's current device is its own)
         flows_bi = list(raft.forward_slicing(clip)) if propagation_steps else None
-        h, w = clip.shape[-2:]
-        kwargs = dict(num_inference_steps=steps, guidance_scale=guidance_scale, noise_level=noise_level,
-                      negative_prompt=negative_prompt, propagation_steps=propagation_steps)
-        if tiling.needs_tiling(h, w, perform_tile):
-            output = tiling.upscale_tiled(pipeline, prompt, clip, flows_bi, generator, tile_size=tile_size, **kwargs)
-        else:
-            output = pipeline(prompt, image=clip, flows_bi=flows_bi, generator=generator, **kwargs).images
-        output = output.squeeze(0).permute(1, 0, 2, 3).contiguous()            # (T,3,4h,4w)
-        if color_fix != "None":
-            source = color_correction.upsample_bicubic4(clip.squeeze(0).permute(1, 0, 2, 3).contiguous())
-            fix = color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix
-            output = fix(output, source)
-        return output.float()
+    if tiling.needs_tiling(h, w, perform_tile):
+        chunks = tiling.upscale_tiled_chunks(pipeline, prompt, clip, flows_bi, generator, tile_size=tile_size, **kwargs)
+    else:
+        denoised = pipeline.denoise(prompt, image=clip, flows_bi=flows_bi, generator=generator, **kwargs)
+        whole = (0, 4 * h, 0, 4 * w)
+        chunks = ((s, f.shape[2], [(whole, f[0])]) for s, f in pipeline.decode_chunks(denoised))
+    for start, n, pieces in chunks:
+        with torch.no_grad(), E.device_guard(clip):
+            if coefs is not None and color_fix == "None":
+                out = (clip.new_empty((n, 4 * h, 4 * w), dtype=torch.uint8),) + tuple(
+                    clip.new_empty((n, 2 * h, 2 * w), dtype=torch.uint8) for _ in range(2))
+                for dst, window in pieces:
+                    _window_to_planes(window, out, dst, coefs)
+            else:
+                out = clip.new_zeros((n, clip.shape[1], 4 * h, 4 * w), dtype=torch.float32)     # "start with black image"
+                for (y0, y1, x0, x1), window in pieces:
+                    out[:, :, y0:y1, x0:x1] = window.permute(1, 0, 2, 3)
+                if color_fix != "None":
+                    source = color_correction.upsample_bicubic4(clip[0, :, start:start + n].permute(1, 0, 2, 3).contiguous())
+                    fix = color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix
+                    out = fix(out, source).float()
+                if coefs is not None:
+                    out = postprocess_planes(out, coefs)
+            del pieces, window                                  # views of the decoder's output: let it go before the next decode
+        yield out
+        del out
+
+
+def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
+                 noise_level, tile_size=256, perform_tile=False, color_fix="None", generator) -> torch.Tensor:
+    """`upscale_clip_chunks` with the frames of all chunks in one tensor (T,3,4h,4w) fp32: the whole 4x clip on the device."""
+    return torch.cat(list(upscale_clip_chunks(
+        pipeline, clip, prompt=prompt, negative_prompt=negative_prompt, raft=raft, propagation_steps=propagation_steps, steps=steps,
+        guidance_scale=guidance_scale, noise_level=noise_level, tile_size=tile_size, perform_tile=perform_tile, color_fix=color_fix,
+        generator=generator)))
