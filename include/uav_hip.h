@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 8
+#define UAV_ABI_VERSION 9
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -541,6 +541,28 @@ int uav_clip_to_yuv420_u8(const float* frames_tchw, void* y, void* cb, void* cr,
 int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride, void* y,
                                  int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch, int64_t c_frame,
                                  int32_t t_len, int32_t h, int32_t w, const int32_t* coefs, void* stream);
+/* The window conversion for every output format of the front end: `chroma444` 0 (4:2:0: Cb, Cr of h/2 x w/2 samples, h and w
+ * even, else UAV_ESHAPE) or 1 (4:4:4: Cb, Cr of h x w samples, any h, w >= 1), `depth` 8 (one byte per sample) or 10 (16-bit
+ * samples 0..1023 in the machine's byte order, little-endian on the hosts this builds for); other values: UAV_EINVAL.  The
+ * source and its three strides are as above.  Plane pitches and frame strides are in SAMPLES, the pointers at the window's
+ * first sample; pitch < the box's width, or overlapping frames when t_len > 1: UAV_ESHAPE; a 16-bit plane pointer at an odd
+ * address: UAV_EALIGN.  Samples outside the window are not touched; vector and scalar accesses give the same result.
+ *
+ * coefs = {fy[3], fcb[3], fcr[3], yo} for both depths (uav.video_io.yuv_coefficients(matrix, full_range, depth).forward); the
+ * chroma centre C and the largest sample M follow from `depth`: C = 128, M = 255 for 8, C = 512, M = 1023 for 10.
+ *   depth 8:  (r, g, b) = the uint8 RGB value as uav_clip_to_frames_u8 forms it; the coefficients are those of
+ *             uav_clip_to_yuv420_u8.  chroma444 = 0 IS uav_clip_window_to_yuv420_u8 (same kernels, same bytes).
+ *   depth 10: no 8-bit intermediate: v = clamp(x/2 + 0.5, 0, 1) in fp32, (r, g, b) = (int)(v * 4095.0f + 0.5f), 12-bit RGB;
+ *             the coefficients are round(k * S / 4095 * 65536) with S = 1023 and yo = 0 for full range, S = 876 (luma) /
+ *             896 (chroma) and yo = 64 for limited range.
+ *   Y = clamp(((fy.rgb + 32768) >> 16) + yo, 0, M), the same Y plane for both chroma layouts;
+ *   4:4:4, per pixel:      Cb = clamp(((fcb.rgb + 32768) >> 16) + C, 0, M), Cr likewise with fcr;
+ *   4:2:0, per 2x2 block:  Cb = clamp(((fcb.sum4 + (1 << 17)) >> 18) + C, 0, M) on the sums of the block's four r, g, b.
+ * All on int32: the largest intermediate is 4 * 4095 * 0.5 * 1023/4095 * 65536 = 1.34e8.  A 10-bit sample lies within 0.75
+ * steps of the exact conversion of the fp32 input (0.5 final rounding + 0.11 12-bit RGB + 0.09 coefficient rounding). */
+int uav_clip_window_to_yuv(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride, void* y,
+                           int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch, int64_t c_frame, int32_t t_len,
+                           int32_t h, int32_t w, int32_t chroma444, int32_t depth, const int32_t* coefs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@
 #   xpmc / attn512   SQ counters of the fused transformer / attention kernels (own --pmc pass);  d = 512 attention at L = 102 400, ring kernel vs attn512w
 #   bench1_lnfold / parity_lnfold   the LayerNorm-fold switch (UAV_LN_FOLD=1): clip time and the headline parity test
 #   yuvio           tools/bench_yuv_io.py: the Y4M front end's Y'CbCr kernels vs the RGB frame conversions, 20 warm launches each (kept copy: profiles/yuv_io_kernels.jsonl)
+#   outfmt          tools/bench_out_format.py: the --out-format kernels (444, 420p10, 444p10) vs uav_clip_to_yuv420_u8 in one process (kept copy: profiles/out_format_kernels.txt)
 # Environment: any UAV_* variable is passed through to every step.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
@@ -144,6 +145,7 @@ PY
     attn512)  timeout 300 python $R/tools/bench_attn512.py 3 2>&1 | grep -v amdgpu.ids | tee $O/${TAG}_attn512.jsonl; UAV_ATTN512X=0 timeout 300 python $R/tools/bench_attn512.py 3 2>&1 | grep -v amdgpu.ids | tee -a $O/${TAG}_attn512.jsonl ;;
     digest)   timeout 200 python $R/tools/conv_digest.py 2>&1 | grep -v amdgpu.ids | tee $O/${TAG}_digest.log ;;
     yuvio)    timeout 300 python $R/tools/bench_yuv_io.py --out $O/${TAG}_yuv_io_kernels.jsonl 2>&1 | grep -v amdgpu.ids ;;
+    outfmt)   timeout 300 python $R/tools/bench_out_format.py --out $O/${TAG}_out_format_kernels.txt 2>&1 | grep -v amdgpu.ids ;;
     *)        echo "unknown step $step" ;;
   esac
 done

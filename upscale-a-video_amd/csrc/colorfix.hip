@@ -421,6 +421,142 @@ __global__ __launch_bounds__(256) void clip_window_to_yuv420_kernel(const float*
     clip_to_yuv420_run<MODE>(in, g.sc, g.sr, yd, g.yp, cbp + co, crp + co, n, k);
 }
 
+// ---- the output formats beside 8-bit 4:2:0: 8-bit 4:4:4 and 10-bit 4:2:0 / 4:4:4 (uav_clip_window_to_yuv) -------------------
+// D10: 16-bit samples 0..1023 made from 12-bit RGB with no 8-bit intermediate, chroma centre 512; else the uint8 RGB value and
+// the luma of the kernels above, chroma centre 128.  C444: a chroma sample per pixel (one rounding each) instead of per 2x2 block.
+template <bool D10> struct YuvDepth { typedef unsigned char sample; static constexpr int centre = 128, vmax = 255; };
+template <> struct YuvDepth<true> { typedef unsigned short sample; static constexpr int centre = 512, vmax = 1023; };
+
+// [-1,1] -> 12-bit value: the clamp of clip_to_u8_kernel, rounded to 0..4095
+UAV_DEVINL int yuv_clip_to_q12(float x) {
+#pragma clang fp contract(off)          // the product is rounded before the sum: a fused multiply-add would move some values by one
+    float v = x / 2.0f + 0.5f;
+    v = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (int)(v * 4095.0f + 0.5f);
+}
+template <bool D10> UAV_DEVINL int yuv_quant(float x) { return D10 ? yuv_clip_to_q12(x) : yuv_clip_to_u8(x); }
+template <bool D10> UAV_DEVINL int yuv_clampd(int v) { return min(max(v, 0), YuvDepth<D10>::vmax); }
+template <bool D10> UAV_DEVINL int yuv_luma_d(const YuvFwd& k, int r, int g, int b) {
+    return yuv_clampd<D10>(((k.fy[0] * r + k.fy[1] * g + k.fy[2] * b + 32768) >> 16) + k.yo);
+}
+// a chroma sample of one pixel / of the R, G, B sums of a 2x2 block
+template <bool D10> UAV_DEVINL int yuv_chroma1(const int* f, int r, int g, int b) {
+    return yuv_clampd<D10>(((f[0] * r + f[1] * g + f[2] * b + 32768) >> 16) + YuvDepth<D10>::centre);
+}
+template <bool D10> UAV_DEVINL int yuv_chroma4(const int* f, int r, int g, int b) {
+    return yuv_clampd<D10>(((f[0] * r + f[1] * g + f[2] * b + (1 << 17)) >> 18) + YuvDepth<D10>::centre);
+}
+// sample j of a run, packed little-endian into 32-bit words
+template <int BYTES> UAV_DEVINL void yuv_pack(uint32_t* words, int j, int v) {
+    if (BYTES == 1) words[j >> 2] |= (uint32_t)v << (8 * (j & 3));
+    else words[j >> 1] |= (uint32_t)v << (16 * (j & 1));
+}
+template <int BYTES> UAV_DEVINL void yuv_store(void* p, const uint32_t* w) {
+    static_assert(BYTES == 4 || BYTES == 8 || BYTES == 16, "one 4-, 8- or 16-byte store");
+    if constexpr (BYTES == 16) { uint4_t v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3]; *reinterpret_cast<uint4_t*>(p) = v; }
+    else if constexpr (BYTES == 8) { uint2_t v; v.x = w[0]; v.y = w[1]; *reinterpret_cast<uint2_t*>(p) = v; }
+    else *reinterpret_cast<uint32_t*>(p) = w[0];
+}
+// BYTES of packed samples as one store (MODE 2) or as two halves (MODE 1)
+template <int MODE, int BYTES> UAV_DEVINL void yuv_store_run(void* p, const uint32_t* w) {
+    if constexpr (MODE == 2) yuv_store<BYTES>(p, w);
+    else {
+        yuv_store<BYTES / 2>(p, w);
+        yuv_store<BYTES / 2>(reinterpret_cast<unsigned char*>(p) + BYTES / 2, w + BYTES / 8);
+    }
+}
+
+// A window of h x w pixels of t_len frames, as clip_window_to_yuv420_kernel, for the three formats above; YuvWindow's plane
+// pitches and frame strides are in SAMPLES here.  4:4:4 takes any h, w >= 1: a thread's run may have one row and an odd length.
+// MODE 2: w % 8 == 0, a run's samples of a row are one store (8 x 8-bit: 8 B, 8 x 16-bit: 16 B, 4 chroma x 16-bit: 8 B);
+// MODE 1: w % 4 == 0, the same as two stores of half the width, a 4-pixel tail is scalar; MODE 0: scalar throughout.
+template <int MODE, bool C444, bool D10>
+__global__ __launch_bounds__(256) void clip_window_to_yuv_kernel(const float* __restrict__ src, void* __restrict__ yv, void* __restrict__ cbv,
+                                                                 void* __restrict__ crv, int h, int w, YuvWindow g, YuvFwd k) {
+    static_assert(C444 || D10, "8-bit 4:2:0 is clip_window_to_yuv420_kernel's");
+    typedef typename YuvDepth<D10>::sample S;
+    constexpr int SB = (int)sizeof(S);
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = (h + 1) / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int rows = min(2, h - y0), n = min(YUV_RUN, w - x0);                  // 4:2:0: rows == 2 and n even
+    const float* in = src + t * g.st + y0 * g.sr + x0;
+    S* yd = reinterpret_cast<S*>(yv) + t * g.yf + y0 * g.yp + x0;
+    const long long co = C444 ? t * g.cf + y0 * g.cp + x0 : t * g.cf + ry * g.cp + (x0 >> 1);
+    S* cbd = reinterpret_cast<S*>(cbv) + co;
+    S* crd = reinterpret_cast<S*>(crv) + co;
+    if (MODE > 0 && n == YUV_RUN) {
+        constexpr int NW = YUV_RUN * SB / 4;                                    // 32-bit words of a run's samples of one row
+        int sr[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r >= rows) break;
+            uint32_t yw[NW], bw[NW], rw[NW];
+#pragma unroll
+            for (int q = 0; q < NW; ++q) yw[q] = bw[q] = rw[q] = 0;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const float* p = in + r * g.sr + q * 4;
+                const float4_t R = *reinterpret_cast<const float4_t*>(p);
+                const float4_t G = *reinterpret_cast<const float4_t*>(p + g.sc);
+                const float4_t B = *reinterpret_cast<const float4_t*>(p + 2 * g.sc);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = q * 4 + j;
+                    const int ir = yuv_quant<D10>(R[j]), ig = yuv_quant<D10>(G[j]), ib = yuv_quant<D10>(B[j]);
+                    yuv_pack<SB>(yw, px, yuv_luma_d<D10>(k, ir, ig, ib));
+                    if (C444) {
+                        yuv_pack<SB>(bw, px, yuv_chroma1<D10>(k.fcb, ir, ig, ib));
+                        yuv_pack<SB>(rw, px, yuv_chroma1<D10>(k.fcr, ir, ig, ib));
+                    } else {
+                        sr[px >> 1] += ir; sg[px >> 1] += ig; sb[px >> 1] += ib;
+                    }
+                }
+            }
+            yuv_store_run<MODE, YUV_RUN * SB>(yd + r * g.yp, yw);
+            if (C444) {
+                yuv_store_run<MODE, YUV_RUN * SB>(cbd + r * g.cp, bw);
+                yuv_store_run<MODE, YUV_RUN * SB>(crd + r * g.cp, rw);
+            }
+        }
+        if constexpr (!C444) {
+            uint32_t bw[2] = {0, 0}, rw[2] = {0, 0};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                yuv_pack<SB>(bw, c, yuv_chroma4<D10>(k.fcb, sr[c], sg[c], sb[c]));
+                yuv_pack<SB>(rw, c, yuv_chroma4<D10>(k.fcr, sr[c], sg[c], sb[c]));
+            }
+            yuv_store_run<MODE, 4 * SB>(cbd, bw);
+            yuv_store_run<MODE, 4 * SB>(crd, rw);
+        }
+        return;
+    }
+    if (C444) {
+        for (int r = 0; r < rows; ++r)
+            for (int j = 0; j < n; ++j) {
+                const float* p = in + r * g.sr + j;
+                const int ir = yuv_quant<D10>(p[0]), ig = yuv_quant<D10>(p[g.sc]), ib = yuv_quant<D10>(p[2 * g.sc]);
+                yd[r * g.yp + j] = (S)yuv_luma_d<D10>(k, ir, ig, ib);
+                cbd[r * g.cp + j] = (S)yuv_chroma1<D10>(k.fcb, ir, ig, ib);
+                crd[r * g.cp + j] = (S)yuv_chroma1<D10>(k.fcr, ir, ig, ib);
+            }
+    } else {
+        for (int c = 0; c < n / 2; ++c) {                                       // one 2x2 block at a time
+            int r4 = 0, g4 = 0, b4 = 0;
+            for (int r = 0; r < 2; ++r)
+                for (int j = 0; j < 2; ++j) {
+                    const float* p = in + r * g.sr + c * 2 + j;
+                    const int ir = yuv_quant<D10>(p[0]), ig = yuv_quant<D10>(p[g.sc]), ib = yuv_quant<D10>(p[2 * g.sc]);
+                    yd[r * g.yp + c * 2 + j] = (S)yuv_luma_d<D10>(k, ir, ig, ib);
+                    r4 += ir; g4 += ig; b4 += ib;
+                }
+            cbd[c] = (S)yuv_chroma4<D10>(k.fcb, r4, g4, b4);
+            crd[c] = (S)yuv_chroma4<D10>(k.fcr, r4, g4, b4);
+        }
+    }
+}
+
 inline bool yuv_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline int yuv_mode(int w, const void* f32, const void* y, const void* cb, const void* cr, bool c444) {
     if (!yuv_aligned(f32, 16)) return 0;
@@ -502,6 +638,57 @@ extern "C" int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stri
     case 1: hipLaunchKernelGGL(clip_window_to_yuv420_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, yp, cbp, crp, h, w, g, k); break;
     default: hipLaunchKernelGGL(clip_window_to_yuv420_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, yp, cbp, crp, h, w, g, k);
     }
+    return uav_launch_status();
+}
+
+namespace {
+template <bool C444, bool D10>
+void clip_window_to_yuv_launch(int mode, dim3 grid, hipStream_t s, const float* src, void* y, void* cb, void* cr, int h, int w,
+                               const YuvWindow& g, const YuvFwd& k) {
+    switch (mode) {
+    case 2: hipLaunchKernelGGL((clip_window_to_yuv_kernel<2, C444, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, g, k); break;
+    case 1: hipLaunchKernelGGL((clip_window_to_yuv_kernel<1, C444, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, g, k); break;
+    default: hipLaunchKernelGGL((clip_window_to_yuv_kernel<0, C444, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, g, k);
+    }
+}
+}  // namespace
+
+extern "C" int uav_clip_window_to_yuv(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride, void* y,
+                                      int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch, int64_t c_frame,
+                                      int32_t t_len, int32_t h, int32_t w, int32_t chroma444, int32_t depth, const int32_t* coefs,
+                                      void* stream) {
+    if (!src || !y || !cb || !cr || !coefs) return UAV_EINVAL;
+    if ((depth != 8 && depth != 10) || (chroma444 != 0 && chroma444 != 1)) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0 || (!chroma444 && ((h & 1) || (w & 1)))) return UAV_ESHAPE;
+    const int ch = chroma444 ? h : h / 2, cw = chroma444 ? w : w / 2;
+    // no negative strides, and the rows / frames of a plane must not overlap (two threads would own one sample)
+    if (src_c_stride < 0 || src_t_stride < 0 || src_row_stride < 0 || y_pitch < w || c_pitch < cw) return UAV_ESHAPE;
+    if (t_len > 1 && (y_frame < (int64_t)(h - 1) * y_pitch + w || c_frame < (int64_t)(ch - 1) * c_pitch + cw)) return UAV_ESHAPE;
+    const uintptr_t sb = depth == 10 ? 2 : 1;                                   // bytes per sample
+    if (!yuv_aligned(y, sb) || !yuv_aligned(cb, sb) || !yuv_aligned(cr, sb)) return UAV_EALIGN;
+    if (!chroma444 && depth == 8)                                               // the format of the entry point above: its kernels
+        return uav_clip_window_to_yuv420_u8(src, src_c_stride, src_t_stride, src_row_stride, y, y_pitch, y_frame, cb, cr, c_pitch,
+                                            c_frame, t_len, h, w, coefs, stream);
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * ((h + 1) / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    YuvFwd k;
+    for (int i = 0; i < 3; ++i) { k.fy[i] = coefs[i]; k.fcb[i] = coefs[3 + i]; k.fcr[i] = coefs[6 + i]; }
+    k.yo = coefs[9];
+    const YuvWindow g = {src_c_stride, src_t_stride, src_row_stride, y_pitch, y_frame, c_pitch, c_frame};
+    // a vector mode holds for every row of every frame only when pointers, strides and pitches keep the alignment: `a` luma
+    // samples per store (8 in mode 2, 4 in mode 1), as many chroma samples in 4:4:4 and half as many in 4:2:0
+    const auto planes_ok = [&](int64_t a) {
+        const int64_t c = chroma444 ? a : a / 2;
+        return w % a == 0 && yuv_aligned(y, a * sb) && (y_pitch | y_frame) % a == 0 && yuv_aligned(cb, c * sb) && yuv_aligned(cr, c * sb) &&
+               (c_pitch | c_frame) % c == 0;
+    };
+    int mode = 0;
+    if ((src_c_stride | src_t_stride | src_row_stride) % 4 == 0 && yuv_aligned(src, 16)) mode = planes_ok(8) ? 2 : planes_ok(4) ? 1 : 0;
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    hipStream_t s = (hipStream_t)stream;
+    if (depth == 8) clip_window_to_yuv_launch<true, false>(mode, grid, s, src, y, cb, cr, h, w, g, k);
+    else if (chroma444) clip_window_to_yuv_launch<true, true>(mode, grid, s, src, y, cb, cr, h, w, g, k);
+    else clip_window_to_yuv_launch<false, true>(mode, grid, s, src, y, cb, cr, h, w, g, k);
     return uav_launch_status();
 }
 

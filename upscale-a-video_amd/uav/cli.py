@@ -12,8 +12,10 @@ or, with no file in between (`-i -` reads one Y4M stream from standard input, `-
 project's `inference_upscale_a_video.py` and does per video what that program does — `video_io.upscale_clip_chunks` — 3 output
 frames at a time: the input is read whole (the DDIM loop needs all of it, at 1/16 of the output's size), the 4x frames go to
 the file chunk by chunk and never exist as one clip.  It reads and writes by itself: YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and
-directories of images in; `.y4m` (4:2:0) out, the colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`,
-`uav_clip_to_yuv420_u8`).  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
+directories of images in; `.y4m` out — `--out-format 420` (8-bit 4:2:0, the default), `444`, `420p10` or `444p10`; the 10-bit
+formats are made from the fp32 frames with no 8-bit step in between and ffmpeg reads all four through the same pipe —, the
+colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`, `uav_clip_to_yuv420_u8`, `uav_clip_window_to_yuv`).
+Input stays 8-bit.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
 each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
 caption text, default none.
 
@@ -71,6 +73,8 @@ def build_parser():
     p.add_argument("--save_suffix", default="")
     p.add_argument("--matrix", default="auto", choices=["auto", "bt601", "bt709"],
                    help="Y'CbCr matrix; auto = BT.709 from 720 rows up, else BT.601, decided separately for input and output size")
+    p.add_argument("--out-format", dest="out_format", default="420", choices=["420", "444", "420p10", "444p10"],
+                   help="Y4M output: 8-bit 4:2:0 (default), 8-bit 4:4:4, or 10-bit 4:2:0 / 4:4:4 (16-bit little-endian samples)")
     p.add_argument("--seed", type=int, default=10)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
@@ -170,6 +174,7 @@ def run(args):
     pipeline, raft = load_pipeline(args.pretrained, use_video_vae=args.use_video_vae, with_propagator=bool(args.propagation_steps),
                                    device=device)
     prompt = args.prompt + args.a_prompt
+    fmt = video_io.out_format(args.out_format)
     out_path = None
     for index, path in enumerate(videos):
         source, fps = first if index == 0 else _read(path)
@@ -186,7 +191,8 @@ def run(args):
         tiles = len(tiling.tile_grid(h, w, args.tile_size)) if tiling.needs_tiling(h, w, args.perform_tile) else 1
         generator = torch.Generator(device=device).manual_seed(args.seed)
         full_range = source.full_range if isinstance(source, video_io.Y4MClip) else True
-        coefs = video_io.yuv_coefficients(video_io.auto_matrix(4 * h) if args.matrix == "auto" else args.matrix, full_range)
+        coefs = video_io.yuv_coefficients(video_io.auto_matrix(4 * h) if args.matrix == "auto" else args.matrix, full_range,
+                                          depth=fmt.depth)
         prop = "_p" + "_".join(map(str, args.propagation_steps)) if args.propagation_steps else ""
         suffix = "_" + args.save_suffix if args.save_suffix else ""
         save_name = f"{name}_n{args.noise_level}_g{args.guidance_scale}_s{args.inference_steps}{prop}{suffix}"
@@ -204,8 +210,9 @@ def run(args):
                                               propagation_steps=args.propagation_steps, steps=args.inference_steps,
                                               guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
                                               perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
-                                              coefs=None if need_frames else coefs)
-        with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, 4 * w, 4 * h, args.fps or fps or 24, full_range) as out:
+                                              coefs=None if need_frames else coefs, fmt=fmt)
+        with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, 4 * w, 4 * h, args.fps or fps or 24, full_range,
+                                fmt) as out:
             for chunk in chunks:                                # one chunk is alive: decoded, converted and written before the next
                 if need_frames:
                     rgb = video_io.postprocess_frames(chunk).cpu().numpy()
@@ -213,7 +220,7 @@ def run(args):
                         _save_png(rgb, os.path.join(args.output_path, "frame", save_name), first=out.frames)
                     if dump is not None:
                         dump.append(rgb)
-                    chunk = video_io.postprocess_planes(chunk, coefs)
+                    chunk = video_io.postprocess_planes(chunk, coefs, fmt)
                 out.write(*chunk)
                 del chunk                                       # before the generator decodes the next one
         if device.type == "cuda":

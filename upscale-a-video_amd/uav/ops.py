@@ -1393,3 +1393,35 @@ def clip_window_to_yuv420_u8(window, y, cb, cr, coefs, frames_first=False):
     rc = lib.uav_clip_window_to_yuv420_u8(_p(window), window.stride(c_dim), window.stride(t_dim), window.stride(2), _p(y), pitch(y),
                                           y.stride(0), _p(cb), _p(cr), pitch(cb), cb.stride(0), t, h, w, k, _stream())
     _lib.check(rc, "uav_clip_window_to_yuv420_u8")
+
+
+def clip_window_to_yuv(window, y, cb, cr, coefs, *, chroma444, depth, frames_first=False):
+    """`clip_window_to_yuv420_u8` for every output format: `chroma444` False (cb, cr (T,h/2,w/2), h and w even) or True (cb, cr
+    (T,h,w), any h, w), `depth` 8 (uint8 planes) or 10 (int16 planes holding 0..1023; 12-bit RGB, no 8-bit intermediate).
+    `coefs`: video_io.yuv_coefficients(matrix, full_range, depth).  Views on both sides, nothing is copied, nothing else written."""
+    lib = _lib.load()
+    if depth not in (8, 10) or chroma444 not in (False, True, 0, 1):
+        raise _lib.UavError(f"clip_window_to_yuv: depth 8 or 10 and chroma444 False or True expected, got {depth!r}, {chroma444!r} (UAV_EINVAL)")
+    if window.dim() != 4 or window.shape[1 if frames_first else 0] != 3:
+        raise _lib.UavError("clip_window_to_yuv: a (3,T,h,w) view expected, (T,3,h,w) with frames_first")
+    c_dim, t_dim = (1, 0) if frames_first else (0, 1)
+    t, (h, w) = window.shape[t_dim], window.shape[2:]
+    if not chroma444 and (h % 2 or w % 2):
+        raise _lib.UavError(f"clip_window_to_yuv: h and w must be even for 4:2:0 planes, got {h}x{w} (UAV_ESHAPE)")
+    if getattr(coefs, "depth", 8) != depth:
+        raise _lib.UavError(f"clip_window_to_yuv: coefficients of depth {getattr(coefs, 'depth', 8)} for planes of depth {depth}")
+    sample = torch.uint8 if depth == 8 else torch.int16
+    cshape = (t, h, w) if chroma444 else (t, h // 2, w // 2)
+    for name, p, dtype, shape in (("window", window, torch.float32, tuple(window.shape)), ("y", y, sample, (t, h, w)),
+                                  ("cb", cb, sample, cshape), ("cr", cr, sample, cshape)):
+        if not p.is_cuda or p.device != window.device or p.dtype != dtype or tuple(p.shape) != shape or p.stride(-1) != 1:
+            raise _lib.UavError(f"clip_window_to_yuv: {name} must be a {dtype} view of shape {shape} with unit pixel stride on "
+                                f"the window's GPU, got {p.dtype} {tuple(p.shape)} strides {p.stride()} on {p.device}")
+    if cb.stride() != cr.stride():
+        raise _lib.UavError("clip_window_to_yuv: cb and cr must share their strides")
+    k = _coef_array(coefs.forward, 10, "clip_window_to_yuv")
+    def pitch(p):                                   # torch leaves the stride of a size-1 dimension arbitrary; no second row is addressed
+        return p.stride(1) if p.shape[1] > 1 else max(p.stride(1), p.shape[2])
+    rc = lib.uav_clip_window_to_yuv(_p(window), window.stride(c_dim), window.stride(t_dim), window.stride(2), _p(y), pitch(y), y.stride(0),
+                                    _p(cb), _p(cr), pitch(cb), cb.stride(0), t, h, w, int(bool(chroma444)), depth, k, _stream())
+    _lib.check(rc, "uav_clip_window_to_yuv")

@@ -8,11 +8,14 @@ Two kernel passes mirror what the reference CLI does with chains of eager tensor
     video = postprocess_frames(output)      # (T,C,H,W) in [-1,1] -> (T,H,W,C) uint8, ready for imageio.mimwrite
 
 and two more take the place of a decoder / encoder's colour conversion for the one container the engine reads and writes
-itself, YUV4MPEG2 (`.y4m`: uncompressed planar 8-bit Y'CbCr, what `ffmpeg -i in.mp4 in.y4m` / `ffmpeg -i out.y4m out.mp4`
+itself, YUV4MPEG2 (`.y4m`: uncompressed planar Y'CbCr, what `ffmpeg -i in.mp4 in.y4m` / `ffmpeg -i out.y4m out.mp4`
 produce and eat), in 16.16 fixed point so that every byte is defined (csrc/colorfix.hip, K13):
 
     clip = preprocess_planes(read_y4m(path), device)        # planes -> (1,3,T,h,w), same normalisation and pooling
     y, cb, cr = postprocess_planes(output, coefs)           # (T,3,H,W) in [-1,1] -> 4:2:0 planes; write_y4m(path, y, cb, cr, ...)
+
+Input is 8-bit (4:2:0 or 4:4:4).  Output is one of `OUT_FORMATS`: '420' (8-bit 4:2:0, the default), '444', '420p10', '444p10' —
+the 10-bit ones from 12-bit RGB with no 8-bit intermediate, 16-bit little-endian samples in the file (`uav_clip_window_to_yuv`).
 
 Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
@@ -30,6 +33,29 @@ YuvCoefs = namedtuple("YuvCoefs", "matrix full_range forward inverse")
 # a decoded .y4m file: uint8 numpy planes y (T,H,W), cb / cr (T,ceil(H/2),ceil(W/2)) [colorspace 'C444': (T,H,W)], fps a Fraction
 # or None, size (H, W), the file's colour-space tag ('' when it has none) and its range
 Y4MClip = namedtuple("Y4MClip", "y cb cr fps size colorspace full_range")
+# an output format: its name, chroma layout, bits per sample, the Y4M `C` tag (None: 'C420jpeg' / 'C420mpeg2' by range, as ever)
+# and the bytes of one sample in the file
+OutFormat = namedtuple("OutFormat", "name chroma444 depth tag sample_bytes")
+OUT_FORMATS = {f.name: f for f in (OutFormat("420", False, 8, None, 1), OutFormat("444", True, 8, "C444", 1),
+                                   OutFormat("420p10", False, 10, "C420p10", 2), OutFormat("444p10", True, 10, "C444p10", 2))}
+
+
+class YuvCoefs10(YuvCoefs):
+    """The forward table of the 10-bit formats, same layout as the 8-bit one (`inverse` is None: input is 8-bit)."""
+    __slots__ = ()
+    depth = 10
+
+
+def out_format(fmt) -> OutFormat:
+    if isinstance(fmt, OutFormat):
+        return fmt
+    if fmt not in OUT_FORMATS:
+        raise ValueError(f"output format must be one of {sorted(OUT_FORMATS)}, got {fmt!r}")
+    return OUT_FORMATS[fmt]
+
+
+def _plane_dtype(fmt: OutFormat):
+    return torch.uint8 if fmt.depth == 8 else torch.int16     # 0..1023 fit; the writer reinterprets them as unsigned
 
 _KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 _CHROMA_420 = ("C420jpeg", "C420mpeg2", "C420paldv", "C420")
@@ -60,13 +86,26 @@ def postprocess_frames(output: torch.Tensor) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------
 # Y'CbCr: integer coefficients, the two device passes
-def yuv_coefficients(matrix: str, full_range: bool) -> YuvCoefs:
+def yuv_coefficients(matrix: str, full_range: bool, depth: int = 8) -> YuvCoefs:
     """16.16 fixed-point tables of both directions for `matrix` in 'bt601' / 'bt709'.  With Kg = 1-Kr-Kb and (ys, yo, cs) =
-    (255, 0, 255) for full range, (219, 16, 224) for limited range, every entry is round(x * 65536) of the textbook value."""
+    (255, 0, 255) for full range, (219, 16, 224) for limited range, every entry is round(x * 65536) of the textbook value.
+    `depth=10`: the forward table only (a `YuvCoefs10`), from 12-bit RGB to 10-bit samples — (ys, yo, cs) = (1023, 0, 1023) for
+    full range, (876, 64, 896) for limited range, entries round(x * s / 4095 * 65536); same layout fy[3], fcb[3], fcr[3], yo."""
     if matrix not in _KR_KB:
         raise ValueError(f"matrix must be one of {sorted(_KR_KB)}, got {matrix!r}")
+    if depth not in (8, 10):
+        raise ValueError(f"depth must be 8 or 10, got {depth!r}")
     kr, kb = _KR_KB[matrix]
     kg = 1.0 - kr - kb
+    if depth == 10:
+        ys, yo, cs = (1023, 0, 1023) if full_range else (876, 64, 896)
+
+        def r12(x):
+            return int(round(x / 4095 * 65536))
+        fy = [r12(kr * ys), r12(kg * ys), r12(kb * ys)]
+        fcb = [r12(-kr / (2 * (1 - kb)) * cs), r12(-kg / (2 * (1 - kb)) * cs), r12(0.5 * cs)]
+        fcr = [r12(0.5 * cs), r12(-kg / (2 * (1 - kr)) * cs), r12(-kb / (2 * (1 - kr)) * cs)]
+        return YuvCoefs10(matrix, bool(full_range), tuple(fy + fcb + fcr + [yo]), None)
     ys, yo, cs = (255, 0, 255) if full_range else (219, 16, 224)
 
     def r(x):
@@ -95,11 +134,29 @@ def preprocess_planes(clip: Y4MClip, device, matrix: str = "auto") -> torch.Tens
         return _pool_large(out).unsqueeze(0)
 
 
-def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs):
+def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs, fmt="420"):
     """(T,3,H,W) in [-1,1] -> uint8 planes Y (T,H,W), Cb, Cr (T,H/2,W/2) on the device: `postprocess_frames`' uint8 RGB value,
-    converted and 2x2-averaged in the same pass (reads the fp32 frames once, writes 1.5 bytes per pixel)."""
+    converted and 2x2-averaged in the same pass (reads the fp32 frames once, writes 1.5 bytes per pixel).  With another `fmt`
+    of `OUT_FORMATS`: the planes of that format — Cb, Cr (T,H,W) for 4:4:4, int16 holding 0..1023 for 10 bits — in one pass too;
+    `coefs` must be of the format's depth."""
+    fmt = out_format(fmt)
     with E.device_guard(output):
-        return ops.clip_to_yuv420_u8(output.float().contiguous(), coefs)
+        frames = output.float().contiguous()
+        if fmt.name == "420":
+            return ops.clip_to_yuv420_u8(frames, coefs)
+        t, _, h, w = frames.shape
+        planes = _new_planes(frames, t, h, w, fmt)
+        ops.clip_window_to_yuv(frames, *planes, coefs, chroma444=fmt.chroma444, depth=fmt.depth, frames_first=True)
+        return planes
+
+
+def _new_planes(like, t, h, w, fmt: OutFormat):
+    """Uninitialised planes of `t` frames of h x w pixels in `fmt` on the device of `like`."""
+    if not fmt.chroma444 and (h % 2 or w % 2):
+        raise ValueError(f"4:2:0 planes need even H and W, got {h}x{w}")
+    ch, cw = (h, w) if fmt.chroma444 else (h // 2, w // 2)
+    dtype = _plane_dtype(fmt)
+    return (like.new_empty((t, h, w), dtype=dtype), like.new_empty((t, ch, cw), dtype=dtype), like.new_empty((t, ch, cw), dtype=dtype))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -168,25 +225,28 @@ def read_y4m(path) -> Y4MClip:
     return Y4MClip(y, cb, cr, fps, (h, w), colorspace, full_range)
 
 
-def y4m_header(w: int, h: int, fps, full_range: bool) -> bytes:
+def y4m_header(w: int, h: int, fps, full_range: bool, fmt="420") -> bytes:
     fps = Fraction(str(fps)) if isinstance(fps, float) else Fraction(fps)
-    return (f"YUV4MPEG2 W{w} H{h} F{fps.numerator}:{fps.denominator} Ip A1:1 {'C420jpeg' if full_range else 'C420mpeg2'} "
+    tag = out_format(fmt).tag or ("C420jpeg" if full_range else "C420mpeg2")
+    return (f"YUV4MPEG2 W{w} H{h} F{fps.numerator}:{fps.denominator} Ip A1:1 {tag} "
             f"XCOLORRANGE={'FULL' if full_range else 'LIMITED'}\n").encode("ascii")
 
 
 class Y4MWriter:
-    """A progressive 4:2:0 YUV4MPEG2 stream written chunk by chunk: the header once, then `write(y, cb, cr)` appends the frames
+    """A progressive YUV4MPEG2 stream written chunk by chunk: the header once, then `write(y, cb, cr)` appends the frames
     of planes Y (n,H,W), Cb, Cr (n,ceil(H/2),ceil(W/2)) — uint8 tensors on any device, or numpy arrays.  Device planes are
     gathered frame by frame on the device and cross to the host as ONE copy per call.  `path_or_file`: an open binary stream
     (a pipe will do: nothing seeks), or a path — then the bytes go to `<path>.part`, which takes the name only on a clean exit:
-    a Y4M file has no frame count, so a file cut short by a failure would look complete."""
+    a Y4M file has no frame count, so a file cut short by a failure would look complete.  `fmt`, one of `OUT_FORMATS`: 4:4:4
+    takes Cb, Cr (n,H,W); the 10-bit formats take int16 tensors (or int16 / uint16 numpy arrays) holding 0..1023 and write
+    every sample as 16 bits, little-endian."""
 
-    def __init__(self, path_or_file, w: int, h: int, fps, full_range: bool):
-        self.w, self.h, self.frames = int(w), int(h), 0
+    def __init__(self, path_or_file, w: int, h: int, fps, full_range: bool, fmt="420"):
+        self.w, self.h, self.frames, self.fmt = int(w), int(h), 0, out_format(fmt)
         self._path = None if hasattr(path_or_file, "write") else os.fspath(path_or_file)
         self._fh = path_or_file if self._path is None else open(self._path + ".part", "wb")
         try:
-            self._fh.write(y4m_header(self.w, self.h, fps, full_range))
+            self._fh.write(y4m_header(self.w, self.h, fps, full_range, self.fmt))
         except BaseException:
             self.close(False)
             raise
@@ -196,17 +256,20 @@ class Y4MWriter:
         if len(y.shape) != 3 or tuple(y.shape[1:]) != (self.h, self.w):
             raise ValueError(f"Y4MWriter: luma planes {tuple(y.shape)}, expected (n, {self.h}, {self.w})")
         t = y.shape[0]
-        cshape = (t, (self.h + 1) // 2, (self.w + 1) // 2)
+        cshape = (t, self.h, self.w) if self.fmt.chroma444 else (t, (self.h + 1) // 2, (self.w + 1) // 2)
         if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
-            raise ValueError(f"Y4MWriter: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for 4:2:0")
+            raise ValueError(f"Y4MWriter: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for "
+                             f"{'4:4:4' if self.fmt.chroma444 else '4:2:0'}")
         if isinstance(y, torch.Tensor):
-            if not y.dtype == cb.dtype == cr.dtype == torch.uint8:
-                raise ValueError("Y4MWriter: uint8 planes expected")
-            frames = torch.cat([p.reshape(t, -1) for p in (y, cb, cr)], dim=1).cpu().numpy()       # (n, bytes of one frame)
+            if not y.dtype == cb.dtype == cr.dtype == _plane_dtype(self.fmt):
+                raise ValueError(f"Y4MWriter: {'uint8' if self.fmt.depth == 8 else 'int16'} planes expected")
+            frames = torch.cat([p.reshape(t, -1) for p in (y, cb, cr)], dim=1).cpu().numpy()       # (n, samples of one frame)
         else:
-            if not y.dtype == cb.dtype == cr.dtype == np.uint8:
-                raise ValueError("Y4MWriter: uint8 planes expected")
+            if not all(p.dtype in ((np.uint8,) if self.fmt.depth == 8 else (np.int16, np.uint16)) for p in (y, cb, cr)):
+                raise ValueError(f"Y4MWriter: {'uint8' if self.fmt.depth == 8 else 'int16 / uint16'} planes expected")
             frames = np.concatenate([np.ascontiguousarray(p).reshape(t, -1) for p in (y, cb, cr)], axis=1)
+        if self.fmt.depth != 8:
+            frames = frames.view(np.uint16).astype("<u2", copy=False)                               # little-endian in the file
         for i in range(t):
             self._fh.write(b"FRAME\n")
             self._fh.write(frames[i].tobytes())
@@ -235,14 +298,16 @@ class Y4MWriter:
         return False
 
 
-def write_y4m(path, y, cb, cr, fps, full_range: bool) -> None:
+def write_y4m(path, y, cb, cr, fps, full_range: bool, fmt="420") -> None:
     """Write 4:2:0 planes Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) (uint8 tensors on any device, or numpy arrays) as a
-    progressive YUV4MPEG2 file: one `Y4MWriter.write`."""
+    progressive YUV4MPEG2 file: one `Y4MWriter.write`.  `fmt`: the planes of another of `OUT_FORMATS`, as `Y4MWriter` takes them."""
+    fmt = out_format(fmt)
     t, h, w = y.shape
-    cshape = (t, (h + 1) // 2, (w + 1) // 2)
+    cshape = (t, h, w) if fmt.chroma444 else (t, (h + 1) // 2, (w + 1) // 2)
     if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
-        raise ValueError(f"write_y4m: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for 4:2:0")
-    with Y4MWriter(path, w, h, fps, full_range) as out:
+        raise ValueError(f"write_y4m: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape} for "
+                         f"{'4:4:4' if fmt.chroma444 else '4:2:0'}")
+    with Y4MWriter(path, w, h, fps, full_range, fmt) as out:
         out.write(y, cb, cr)
 
 
@@ -276,16 +341,20 @@ def read_frames(path):
 
 
 # ------------------------------------------------------------------------------------------------
-def _window_to_planes(window, planes, dst, coefs):
+def _window_to_planes(window, planes, dst, coefs, fmt=OUT_FORMATS["420"]):
     """One piece of a chunk — `window` (3,n,dy,dx), a view of decoder output — converted into the box `dst` = (y0, y1, x0, x1)
     of the chunk's planes Y (n,H,W), Cb, Cr (n,H/2,W/2).  On the device this is ONE kernel that reads the view in place and
     writes the box (`ops.clip_window_to_yuv420_u8`).  The only place that decides about host tensors: `uav.ops` has no CPU
     path — every op raises `UavError` for a host tensor, and so does this one in production — but the CPU tests swap
     `ops.clip_to_yuv420_u8` for a torch stand-in (tests/cpu_ops_io.py) and know nothing of newer symbols, so a host window
-    goes through that entry point on a contiguous copy and is placed with torch indexing."""
+    goes through that entry point on a contiguous copy and is placed with torch indexing.  The other formats of `OUT_FORMATS`
+    are `ops.clip_window_to_yuv` for every window (the CPU tests swap that one op: tests/cpu_ops_fmt.py)."""
     y0, y1, x0, x1 = dst
-    boxes = [p[:, a:b, c:d] for p, (a, b, c, d) in zip(planes, ((y0, y1, x0, x1),) + ((y0 // 2, y1 // 2, x0 // 2, x1 // 2),) * 2)]
-    if window.is_cuda:
+    cbox = (y0, y1, x0, x1) if fmt.chroma444 else (y0 // 2, y1 // 2, x0 // 2, x1 // 2)
+    boxes = [p[:, a:b, c:d] for p, (a, b, c, d) in zip(planes, ((y0, y1, x0, x1), cbox, cbox))]
+    if fmt.name != "420":
+        ops.clip_window_to_yuv(window, *boxes, coefs, chroma444=fmt.chroma444, depth=fmt.depth)
+    elif window.is_cuda:
         ops.clip_window_to_yuv420_u8(window, *boxes, coefs)
     else:
         for box, plane in zip(boxes, ops.clip_to_yuv420_u8(window.permute(1, 0, 2, 3).contiguous(), coefs)):
@@ -293,19 +362,20 @@ def _window_to_planes(window, planes, dst, coefs):
 
 
 def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
-                        noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None):
+                        noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None, fmt="420"):
     """What the upscaling program does with one video between reading and writing it, in its order, 3 output frames at a time:
     bidirectional flows of the whole clip when propagation steps are asked for, then the DDIM loop of the whole clip — of
     every tile (`tiling.needs_tiling`: asked for, or h*w >= 384*384), or of the one pipeline call — whose results live at the
     input resolution, then per chunk the decode and the optional colour fix against the bicubically up-sampled input frames
     of that chunk (statistics, blur and resize are per frame).  `clip`: (1,3,T,h,w) in [-1,1] (preprocess_frames /
     preprocess_planes).  A generator of the chunks' frames (n,3,4h,4w) fp32, n <= 3 — or, with `coefs`, of their 4:2:0 planes
-    (y, cb, cr) as `postprocess_planes` returns them; without a colour fix those are converted straight from the decoder's
-    output, tile by tile, and no fp32 frame of the 4x clip is assembled at all."""
+    (y, cb, cr) as `postprocess_planes` returns them, in the output format `fmt` (`coefs` of its depth); without a colour fix those
+    are converted straight from the decoder's output, tile by tile, and no fp32 frame of the 4x clip is assembled at all."""
     from models_video import color_correction
     from . import tiling
     if color_fix not in ("None", "AdaIn", "Wavelet"):
         raise ValueError(f"color_fix must be 'None', 'AdaIn' or 'Wavelet', got {color_fix!r}")
+    fmt = out_format(fmt)
     propagation_steps = list(propagation_steps)
     if propagation_steps and raft is None:
         raise ValueError("propagation steps need a flow estimator (raft=...)")
@@ -322,11 +392,14 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
         chunks = ((s, f.shape[2], [(whole, f[0])]) for s, f in pipeline.decode_chunks(denoised))
     for start, n, pieces in chunks:
         with torch.no_grad(), E.device_guard(clip):
+            window = None
             if coefs is not None and color_fix == "None":
-                out = (clip.new_empty((n, 4 * h, 4 * w), dtype=torch.uint8),) + tuple(
-                    clip.new_empty((n, 2 * h, 2 * w), dtype=torch.uint8) for _ in range(2))
+                out = _new_planes(clip, n, 4 * h, 4 * w, fmt)
                 for dst, window in pieces:
-                    _window_to_planes(window, out, dst, coefs)
+                    _window_to_planes(window, out, dst, coefs, fmt)
+                if window is None:          # no tile at all (`tile_grid` drops the only row or column of a frame no larger than
+                    # the overlap): the planes of the black canvas the other path starts with
+                    out = postprocess_planes(clip.new_zeros((n, clip.shape[1], 4 * h, 4 * w), dtype=torch.float32), coefs, fmt)
             else:
                 out = clip.new_zeros((n, clip.shape[1], 4 * h, 4 * w), dtype=torch.float32)     # "start with black image"
                 for (y0, y1, x0, x1), window in pieces:
@@ -336,7 +409,7 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
                     fix = color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix
                     out = fix(out, source).float()
                 if coefs is not None:
-                    out = postprocess_planes(out, coefs)
+                    out = postprocess_planes(out, coefs, fmt)
             del pieces, window                                  # views of the decoder's output: let it go before the next decode
         yield out
         del out
