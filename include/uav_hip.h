@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 9
+#define UAV_ABI_VERSION 10
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -432,6 +432,40 @@ int uav_resize_bicubic_f32(const float* src, float* dst, int32_t planes, int32_t
  * Propagation.forward (propagation_module.py:206-209) when flows and latents differ in resolution */
 int uav_resize_area_f32(const float* src, float* dst, int32_t planes, int32_t hi, int32_t wi, int32_t ho, int32_t wo,
                         float mul, void* stream);
+
+/* ABI v10.  Antialiased separable cubic resize of fp32 planes (planes, hi, wi) -> (planes, ho, wo): the filter of
+ * F.interpolate(mode='bicubic', antialias=True) (ATen _upsample_bicubic2d_aa, Pillow's BICUBIC) per axis, horizontal pass first,
+ * fp32 intermediate (planes, hi, wo) in the workspace.  What stands between the decoder's 4x frames and the encoder for
+ * `--out-size` / `--out-scale` of the front end: uav_resize_bicubic_f32 aliases when it shrinks, uav_resize_area_f32 is a box.
+ *
+ * For an axis with n_in source and n_out result samples and result index i:
+ *   s = n_in / n_out            c = s * (i + 0.5)
+ *   support = 2*s if s >= 1 else 2          inv = 1/s if s >= 1 else 1
+ *   lo = max(0, floor(c - support + 0.5))   hi = min(n_in, floor(c + support + 0.5))
+ *   k_j = cubic((j + 0.5 - c) * inv), j in [lo, hi)      w_j = k_j / sum_j k_j      out_i = sum_j w_j * in_j
+ * with the Keys cubic, A = -0.5:
+ *   cubic(x) = ((A+2)|x| - (A+3))|x|^2 + 1   for |x| < 1,     A(((|x| - 5)|x| + 8)|x| - 4)   for |x| < 2,     0 beyond.
+ * Borders truncate the tap range and renormalise; there is no clamped replication.  At most ceil(4s) taps when shrinking, 4
+ * otherwise.
+ *
+ * Positions are exact: lo and hi are int64 floor divisions — lo = floor(((2i+1) n_in - 4 max(n_in, n_out) + n_out) / (2 n_out)),
+ * hi likewise with + 4 max(..) — and the argument of tap j is the one quotient ((2j+1) n_out - (2i+1) n_in) / (2 max(n_in, n_out)),
+ * divided in fp64 and rounded to fp32 once (torch forms c in fp32: its error grows with the index, ~1e-3 at 4K widths).  cubic,
+ * the sum (ascending j) and w_j = k_j / sum are fp32.  Equal sizes give the weights (0, 1, 0, 0): a copy of every finite value up to
+ * the sign of zero (the taps are still summed: -0.0 comes back as +0.0, and a sample next to an Inf or NaN comes back NaN).
+ * A result sample is ONE fp32 accumulator, acc = fmaf(w_j, in_j, acc) in ascending j from 0; vector (16-byte, when the row
+ * lengths are multiples of 4 and the pointers 16-byte aligned) and scalar accesses give the same bits, there are no atomics, and
+ * two calls give identical results.
+ *
+ * uav_resize_aa_workspace_bytes: the intermediate plus the tap tables (first tap, count and weights per result column and
+ * row, written by a set-up launch of the same call); UAV_ESHAPE (negative) for a shape uav_resize_aa_f32 refuses.
+ * Refusals, before any launch: a null src / dst / workspace: UAV_EINVAL; one of them not 4-byte aligned: UAV_EALIGN; planes
+ * outside 1..65535, a size < 1, n_in > 64 * n_out on either axis (bounds the taps at 257), ho > 262140 or wo > 16776960 (grid
+ * limits), or workspace_bytes below uav_resize_aa_workspace_bytes(...): UAV_ESHAPE.  Nothing outside dst[planes*ho*wo] and
+ * workspace[0 .. that many bytes) is written. */
+int64_t uav_resize_aa_workspace_bytes(int32_t planes, int32_t hi, int32_t wi, int32_t ho, int32_t wo);
+int uav_resize_aa_f32(const float* src, float* dst, int32_t planes, int32_t hi, int32_t wi, int32_t ho, int32_t wo,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- K10: flow-guided propagation step -----------------------------------------------
  * Replaces one recurrence step of Propagation.forward (propagation_module.py:234-254) with

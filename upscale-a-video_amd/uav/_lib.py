@@ -123,6 +123,8 @@ SIGNATURES = {
     "uav_atrous_blur_f32": (C.c_int, [c_p, c_p, c_p, i32, i32, i32, i32, c_p]),
     "uav_resize_bicubic_f32": (C.c_int, [c_p, c_p, i32, i32, i32, i32, i32, f32, f32, c_p]),
     "uav_resize_area_f32": (C.c_int, [c_p, c_p, i32, i32, i32, i32, i32, f32, c_p]),
+    "uav_resize_aa_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "uav_resize_aa_f32": (C.c_int, [c_p, c_p, i32, i32, i32, i32, i32, c_p, i64, c_p]),
     "uav_conv_gemm_f32": (C.c_int, [C.POINTER(ConvParams), c_p]),
     "uav_instnorm_f32": (C.c_int, [c_p, c_p, i32, i32, i32, f32, i32, c_p]),
     "uav_add_relu_f32": (C.c_int, [c_p, c_p, c_p, i64, i32, c_p]),
@@ -137,7 +139,7 @@ SIGNATURES = {
     "uav_propagate_step_f32": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i64, i64, i32, f32, f32, f32, c_p]),
 }
 
-EXPECTED_ABI = 9          # include/uav_hip.h UAV_ABI_VERSION this binding was written against
+EXPECTED_ABI = 10         # include/uav_hip.h UAV_ABI_VERSION this binding was written against
 
 
 class UavError(RuntimeError):

@@ -1,4 +1,4 @@
-"""The engine's own upscaling program: video files in, 4x video files out, on one MI355X.
+"""The engine's own upscaling program: video files in, 4x video files out (or any size from 1x to 4x), on one MI355X.
 
     ffmpeg -i in.mp4 in.y4m                                                   # on the user's side: any container -> YUV4MPEG2
     python upscale.py -i in.y4m -o results --pretrained pretrained_models/upscale_a_video
@@ -15,7 +15,11 @@ the file chunk by chunk and never exist as one clip.  It reads and writes by its
 directories of images in; `.y4m` out — `--out-format 420` (8-bit 4:2:0, the default), `444`, `420p10` or `444p10`; the 10-bit
 formats are made from the fp32 frames with no 8-bit step in between and ffmpeg reads all four through the same pipe —, the
 colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`, `uav_clip_to_yuv420_u8`, `uav_clip_window_to_yuv`).
-Input stays 8-bit.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
+Input stays 8-bit.  `--out-size WxH` (or `W:H`) or `--out-scale S` (1 to 4) write another size than 4x, from the network's input
+size up to 4x of it: 480p material at 1080p is `--out-scale 2.25`.  Each chunk's fp32 frames are resized on the GPU with an
+antialiased cubic filter (`uav_resize_aa_f32`: the filter of `F.interpolate(mode='bicubic', antialias=True)`, after the colour
+fix and before the colour conversion), so only frames of the delivery size reach the host; `--matrix auto` goes by the rows
+written.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
 each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
 caption text, default none.
 
@@ -75,12 +79,47 @@ def build_parser():
                    help="Y'CbCr matrix; auto = BT.709 from 720 rows up, else BT.601, decided separately for input and output size")
     p.add_argument("--out-format", dest="out_format", default="420", choices=["420", "444", "420p10", "444p10"],
                    help="Y4M output: 8-bit 4:2:0 (default), 8-bit 4:4:4, or 10-bit 4:2:0 / 4:4:4 (16-bit little-endian samples)")
+    p.add_argument("--out-size", dest="out_size", metavar="WxH", default=None,
+                   help="size of the frames written (also W:H), from the network's input size up to 4x of it; default 4x")
+    p.add_argument("--out-scale", dest="out_scale", metavar="S", default=None,
+                   help="the same as a factor of the network's input size, 1 to 4 (2.25: 480p -> 1080p); sides are rounded to even")
     p.add_argument("--seed", type=int, default=10)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
     p.add_argument("--dump-rgb", dest="dump_rgb", metavar="FILE", default=None,
                    help="write the uint8 RGB frames (T,H,W,3) of the last video as .npy (tests, A/B runs)")
     return p
+
+
+def _out_size_options(args):
+    """`--out-size` / `--out-scale` as `video_io.output_size` takes them: ((W, H) or None, S or None)."""
+    if args.out_size is not None and args.out_scale is not None:
+        raise UserError("--out-size and --out-scale exclude each other")
+    size = scale = None
+    if args.out_size is not None:
+        parts = args.out_size.lower().replace(":", "x").split("x")
+        if len(parts) != 2 or not all(v.isascii() and v.isdigit() for v in parts) or not all(int(v) > 0 for v in parts):
+            raise UserError(f"--out-size: not a size: {args.out_size!r} (e.g. 1920x1080 or 1920:1080)")
+        size = (int(parts[0]), int(parts[1]))
+    if args.out_scale is not None:
+        try:
+            scale = float(args.out_scale)
+        except ValueError:
+            scale = float("nan")
+        if not 1.0 <= scale <= 4.0:
+            raise UserError(f"--out-scale: a factor from 1 to 4 expected, got {args.out_scale!r}")
+    return size, scale
+
+
+def _output_size(source, size, scale, fmt):
+    """(H, W) to write for one video read by `_read`; a size outside the video's range is a UserError."""
+    from . import video_io
+    in_h, in_w = source.size if isinstance(source, video_io.Y4MClip) else source.shape[1:3]
+    h, w = video_io.pooled_size(int(in_h), int(in_w))
+    try:
+        return video_io.output_size(4 * h, 4 * w, out_size=size, out_scale=scale, fmt=fmt)
+    except ValueError as e:
+        raise UserError(f"--out-size: {e}" if size is not None else f"--out-scale: {e}") from None
 
 
 def _need(path, what):
@@ -164,6 +203,7 @@ def _read(path):
 
 def run(args):
     from . import tiling, video_io
+    size, scale = _out_size_options(args)
     videos = ["-"] if args.input_path == "-" else list_videos(args.input_path)
     if args.y4m_out is not None and len(videos) > 1:
         raise UserError(f"--y4m-out takes one video, {args.input_path} holds {len(videos)}")
@@ -171,14 +211,16 @@ def run(args):
     if device.type == "cuda" and not torch.cuda.is_available():
         raise UserError(f"--device {args.device}: no GPU is visible")
     first = _read(videos[0])                # before the checkpoints are loaded: an unreadable input fails at once
+    fmt = video_io.out_format(args.out_format)
+    _output_size(first[0], size, scale, fmt)                # ... and so does a size the first video cannot have
     pipeline, raft = load_pipeline(args.pretrained, use_video_vae=args.use_video_vae, with_propagator=bool(args.propagation_steps),
                                    device=device)
     prompt = args.prompt + args.a_prompt
-    fmt = video_io.out_format(args.out_format)
     out_path = None
     for index, path in enumerate(videos):
         source, fps = first if index == 0 else _read(path)
         first = None
+        out_h, out_w = _output_size(source, size, scale, fmt)
         name = "stdin" if path == "-" else os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
         if isinstance(source, video_io.Y4MClip):
             clip = video_io.preprocess_planes(source, device, args.matrix)
@@ -191,7 +233,7 @@ def run(args):
         tiles = len(tiling.tile_grid(h, w, args.tile_size)) if tiling.needs_tiling(h, w, args.perform_tile) else 1
         generator = torch.Generator(device=device).manual_seed(args.seed)
         full_range = source.full_range if isinstance(source, video_io.Y4MClip) else True
-        coefs = video_io.yuv_coefficients(video_io.auto_matrix(4 * h) if args.matrix == "auto" else args.matrix, full_range,
+        coefs = video_io.yuv_coefficients(video_io.auto_matrix(out_h) if args.matrix == "auto" else args.matrix, full_range,
                                           depth=fmt.depth)
         prop = "_p" + "_".join(map(str, args.propagation_steps)) if args.propagation_steps else ""
         suffix = "_" + args.save_suffix if args.save_suffix else ""
@@ -210,8 +252,9 @@ def run(args):
                                               propagation_steps=args.propagation_steps, steps=args.inference_steps,
                                               guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
                                               perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
-                                              coefs=None if need_frames else coefs, fmt=fmt)
-        with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, 4 * w, 4 * h, args.fps or fps or 24, full_range,
+                                              coefs=None if need_frames else coefs, fmt=fmt,
+                                              out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w))
+        with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, out_w, out_h, args.fps or fps or 24, full_range,
                                 fmt) as out:
             for chunk in chunks:                                # one chunk is alive: decoded, converted and written before the next
                 if need_frames:
@@ -230,7 +273,7 @@ def run(args):
             import numpy as np
             with open(args.dump_rgb, "wb") as fh:
                 np.save(fh, np.concatenate(dump))
-        print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {4 * h}x{4 * w}, {tiles} tile(s), "
+        print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {out_h}x{out_w}, {tiles} tile(s), "
               f"{seconds:.2f} s -> {out_path}", file=sys.stderr if out_path == "-" else sys.stdout, flush=True)
     return out_path
 

@@ -1299,6 +1299,25 @@ def resize_area_f32(x, ho, wo, mul=1.0):
     return out
 
 
+def resize_aa_f32(x, ho, wo):
+    """F.interpolate(x, (ho, wo), mode='bicubic', antialias=True) on (..., H, W) fp32 with exact sample positions
+    (uav_resize_aa_f32): the leading dimensions are the planes; the workspace — the (planes, H, wo) intermediate and the tap
+    tables — comes from torch's allocator for the call.  `x` must be contiguous (no hidden copy of a 4x chunk)."""
+    lib = _lib.load()
+    _req(x, F32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise _lib.UavError("resize_aa_f32: a non-empty (..., H, W) tensor expected")
+    hi, wi = x.shape[-2:]
+    planes, ho, wo = x.numel() // (hi * wi), int(ho), int(wo)
+    nb = lib.uav_resize_aa_workspace_bytes(planes, hi, wi, ho, wo)
+    if nb < 0:
+        _lib.check(nb, f"uav_resize_aa_workspace_bytes({planes}, {hi}x{wi} -> {ho}x{wo})")
+    out = torch.empty(tuple(x.shape[:-2]) + (ho, wo), dtype=F32, device=x.device)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    _lib.check(lib.uav_resize_aa_f32(_p(x), _p(out), planes, hi, wi, ho, wo, _p(ws), nb, _stream()), "uav_resize_aa_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # frame I/O conversions of the CLI (K13, SURVEY §8 row f4)
 def frames_to_clip_f32(frames):

@@ -17,6 +17,11 @@ produce and eat), in 16.16 fixed point so that every byte is defined (csrc/color
 Input is 8-bit (4:2:0 or 4:4:4).  Output is one of `OUT_FORMATS`: '420' (8-bit 4:2:0, the default), '444', '420p10', '444p10' —
 the 10-bit ones from 12-bit RGB with no 8-bit intermediate, 16-bit little-endian samples in the file (`uav_clip_window_to_yuv`).
 
+Output size: the network's result is 4x its input; `output_size` turns the program's `--out-size WxH` / `--out-scale S` into any
+(H, W) between 1x and 4x, and `upscale_clip_chunks(..., out_size=(H, W))` resizes every chunk's fp32 frames on the device with the
+antialiased cubic filter of `ops.resize_aa_f32` (csrc/resize_aa.hip) before they are converted, so nothing larger than the
+delivery size crosses to the host.
+
 Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
 import os
@@ -70,10 +75,15 @@ def preprocess_frames(frames: torch.Tensor) -> torch.Tensor:
         return _pool_large(clip).unsqueeze(0)
 
 
+def pooled_size(h: int, w: int):
+    """The size the network sees for frames of h x w: those of 1280 pixels and more on both sides are area-pooled by 4."""
+    return (h // 4, w // 4) if h >= 1280 and w >= 1280 else (h, w)
+
+
 def _pool_large(clip):
-    h, w = clip.shape[-2:]
-    if h >= 1280 and w >= 1280:
-        clip = ops.resize_area_f32(clip, int(h // 4), int(w // 4))
+    h, w = (int(v) for v in clip.shape[-2:])
+    if pooled_size(h, w) != (h, w):
+        clip = ops.resize_area_f32(clip, *pooled_size(h, w))
     return clip
 
 
@@ -121,6 +131,34 @@ def yuv_coefficients(matrix: str, full_range: bool, depth: int = 8) -> YuvCoefs:
 def auto_matrix(rows: int) -> str:
     """The usual convention for untagged material: BT.709 from 720 rows up, BT.601 below."""
     return "bt709" if rows >= 720 else "bt601"
+
+
+def output_size(h4: int, w4: int, *, out_size=None, out_scale=None, fmt):
+    """The (H, W) of the frames to write for a network result of h4 x w4 (4x its input).  At most one of: `out_size` = (W, H),
+    taken as given — ValueError unless h4/4 <= H <= h4 and w4/4 <= W <= w4, and for an odd side with a 4:2:0 format `fmt`;
+    `out_scale` = S in [1, 4] — each side 2*floor(S*side/2 + 0.5) of the network's input side (h4/4, w4/4), clipped to the even
+    sizes of that range, so it suits every format.  Neither: (h4, w4)."""
+    fmt = out_format(fmt)
+    if out_size is not None and out_scale is not None:
+        raise ValueError("give an output size or an output scale, not both")
+    h1, w1 = -(-h4 // 4), -(-w4 // 4)
+    span = f"{w1}x{h1} to {w4}x{h4}"
+    if out_size is not None:
+        w, h = (int(v) for v in out_size)
+        if not (h1 <= h <= h4 and w1 <= w <= w4):
+            raise ValueError(f"output size {w}x{h} is outside {span} (1x to 4x of the network's input)")
+        if not fmt.chroma444 and (h % 2 or w % 2):
+            raise ValueError(f"output size {w}x{h}: the 4:2:0 format {fmt.name} needs even sides ({span}, even)")
+        return h, w
+    if out_scale is not None:
+        scale = float(out_scale)
+        if not 1.0 <= scale <= 4.0:
+            raise ValueError(f"output scale {out_scale} is outside 1 to 4 ({span})")
+
+        def side(n1, n4):
+            return min(max(2 * int(scale * n1 / 2 + 0.5), n1 + n1 % 2), n4 - n4 % 2)
+        return side(h1, h4), side(w1, w4)
+    return h4, w4
 
 
 def preprocess_planes(clip: Y4MClip, device, matrix: str = "auto") -> torch.Tensor:
@@ -362,7 +400,8 @@ def _window_to_planes(window, planes, dst, coefs, fmt=OUT_FORMATS["420"]):
 
 
 def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
-                        noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None, fmt="420"):
+                        noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None, fmt="420",
+                        out_size=None):
     """What the upscaling program does with one video between reading and writing it, in its order, 3 output frames at a time:
     bidirectional flows of the whole clip when propagation steps are asked for, then the DDIM loop of the whole clip — of
     every tile (`tiling.needs_tiling`: asked for, or h*w >= 384*384), or of the one pipeline call — whose results live at the
@@ -370,7 +409,13 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     of that chunk (statistics, blur and resize are per frame).  `clip`: (1,3,T,h,w) in [-1,1] (preprocess_frames /
     preprocess_planes).  A generator of the chunks' frames (n,3,4h,4w) fp32, n <= 3 — or, with `coefs`, of their 4:2:0 planes
     (y, cb, cr) as `postprocess_planes` returns them, in the output format `fmt` (`coefs` of its depth); without a colour fix those
-    are converted straight from the decoder's output, tile by tile, and no fp32 frame of the 4x clip is assembled at all."""
+    are converted straight from the decoder's output, tile by tile, and no fp32 frame of the 4x clip is assembled at all.
+
+    `out_size` = (H, W) other than (4h, 4w), within `output_size`'s range: every chunk is assembled as fp32 frames at 4x (the
+    colour fix's branch; resampling crosses tile borders, so the tile-by-tile conversion cannot serve), colour-fixed at 4x when
+    asked, resized to (n,3,H,W) with `ops.resize_aa_f32` and converted then.  That costs, per chunk of 3 frames and beside the
+    decoder's output, the fp32 frames at 4x (3*3*4h*4w*4 bytes), the resizer's intermediate (3*3*4h*W*4) and its result
+    (3*3*H*W*4).  `None` or (4h, 4w): today's path, unchanged."""
     from models_video import color_correction
     from . import tiling
     if color_fix not in ("None", "AdaIn", "Wavelet"):
@@ -380,6 +425,9 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     if propagation_steps and raft is None:
         raise ValueError("propagation steps need a flow estimator (raft=...)")
     h, w = clip.shape[-2:]
+    if out_size is not None:
+        out_h, out_w = output_size(4 * h, 4 * w, out_size=(out_size[1], out_size[0]), fmt=fmt if coefs is not None else "444")
+        out_size = None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w)
     kwargs = dict(num_inference_steps=steps, guidance_scale=guidance_scale, noise_level=noise_level,
                   negative_prompt=negative_prompt, propagation_steps=propagation_steps)
     with torch.no_grad(), E.device_guard(clip):          # (no guard is held across a `yield`: the caller's current device is its own)
@@ -393,7 +441,7 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     for start, n, pieces in chunks:
         with torch.no_grad(), E.device_guard(clip):
             window = None
-            if coefs is not None and color_fix == "None":
+            if coefs is not None and color_fix == "None" and out_size is None:
                 out = _new_planes(clip, n, 4 * h, 4 * w, fmt)
                 for dst, window in pieces:
                     _window_to_planes(window, out, dst, coefs, fmt)
@@ -408,6 +456,8 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
                     source = color_correction.upsample_bicubic4(clip[0, :, start:start + n].permute(1, 0, 2, 3).contiguous())
                     fix = color_correction.adain_color_fix if color_fix == "AdaIn" else color_correction.wavelet_color_fix
                     out = fix(out, source).float()
+                if out_size is not None:
+                    out = ops.resize_aa_f32(out.contiguous(), *out_size)
                 if coefs is not None:
                     out = postprocess_planes(out, coefs, fmt)
             del pieces, window                                  # views of the decoder's output: let it go before the next decode
@@ -416,9 +466,10 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
 
 
 def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
-                 noise_level, tile_size=256, perform_tile=False, color_fix="None", generator) -> torch.Tensor:
-    """`upscale_clip_chunks` with the frames of all chunks in one tensor (T,3,4h,4w) fp32: the whole 4x clip on the device."""
+                 noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, out_size=None) -> torch.Tensor:
+    """`upscale_clip_chunks` with the frames of all chunks in one tensor (T,3,4h,4w) fp32: the whole 4x clip on the device —
+    (T,3,H,W) with `out_size` = (H, W)."""
     return torch.cat(list(upscale_clip_chunks(
         pipeline, clip, prompt=prompt, negative_prompt=negative_prompt, raft=raft, propagation_steps=propagation_steps, steps=steps,
         guidance_scale=guidance_scale, noise_level=noise_level, tile_size=tile_size, perform_tile=perform_tile, color_fix=color_fix,
-        generator=generator)))
+        generator=generator, out_size=out_size)))
