@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 10
+#define UAV_ABI_VERSION 11
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -597,6 +597,34 @@ int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stride, int64_t
 int uav_clip_window_to_yuv(const float* src, int64_t src_c_stride, int64_t src_t_stride, int64_t src_row_stride, void* y,
                            int64_t y_pitch, int64_t y_frame, void* cb, void* cr, int64_t c_pitch, int64_t c_frame, int32_t t_len,
                            int32_t h, int32_t w, int32_t chroma444, int32_t depth, const int32_t* coefs, void* stream);
+
+/* Siting-aware 4:2:0 (the front end's `--chroma sited`).  uav_yuv420_to_clip_f32 replicates a chroma sample over its 2x2 block and
+ * uav_clip_to_yuv420_u8 / uav_clip_window_to_yuv write the block's mean, a sample at the block's centre; these two filter at the
+ * position the Y4M tag declares.  Same tables, same int32 arithmetic, every output defined bit for bit.
+ *
+ * Decode: planes Y (T,H,W), Cb, Cr (T,ceil(H/2),ceil(W/2)) uint8 -> clip (3,T,H,W) fp32 in [-1,1], any H, W >= 1, with bilinear
+ * chroma up-sampling.  `centre_h` / `centre_v`: 1 when the chroma sample lies between its two luma samples on that axis, 0 when it
+ * lies on the even one (C420jpeg: 1, 1; C420mpeg2: 0, 1; C420paldv as ffmpeg maps it, top-left: 0, 0); other values: UAV_EINVAL.
+ * Per axis, for luma index x and chroma index i = x >> 1, indices clamped to the plane, weights in quarters:
+ *   centre:    even x: c[i-1] + 3 c[i]      odd x: 3 c[i] + c[i+1]
+ *   co-sited:  even x: 4 c[i]               odd x: 2 c[i] + 2 c[i+1]
+ * The two axes multiply (sixteenths): u16 = sum wv*wh*Cb - 2048, v16 = sum wv*wh*Cr - 2048.  coefs = {yo, iy, rcr, gcb, gcr, bcb}
+ * as uav_yuv420_to_clip_f32; yy = (Y-yo)*iy and ONE rounding:
+ *   R = clamp((16*yy + rcr*v16 + (1 << 19)) >> 20, 0, 255), G = clamp((16*yy + gcb*u16 + gcr*v16 + (1 << 19)) >> 20, 0, 255),
+ *   B = clamp((16*yy + bcb*u16 + (1 << 19)) >> 20, 0, 255), then `(v/255. - 0.5) * 2`.
+ * The largest intermediate is below 2^29.2.  Constant chroma planes give uav_yuv420_to_clip_f32's result. */
+int uav_yuv420_sited_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                                 int32_t w, int32_t centre_h, int32_t centre_v, const int32_t* coefs, void* stream);
+/* Encode, horizontally co-sited and vertically centred (the siting of `C420mpeg2` and `C420p10`): contiguous frames (T,3,H,W) fp32
+ * in [-1,1], H and W even (else UAV_ESHAPE) -> contiguous planes Y (T,H,W), Cb, Cr (T,H/2,W/2); `depth` 8 (uint8 planes) or 10
+ * (16-bit samples 0..1023; a plane pointer at an odd address: UAV_EALIGN); other depths: UAV_EINVAL.  coefs = {fy[3], fcb[3],
+ * fcr[3], yo}, q = (r, g, b), C and M exactly as uav_clip_window_to_yuv forms them for that depth (the uint8 RGB value / 12-bit
+ * RGB; C = 128, M = 255 / C = 512, M = 1023), and the same Y plane.  Chroma sample (j, i), columns clamped to the frame:
+ *   S = sum over rows 2j, 2j+1 of (q[2i-1] + 2 q[2i] + q[2i+1])      per r, g, b; the weights total 8
+ *   Cb = clamp(((fcb.S + (1 << 18)) >> 19) + C, 0, M), Cr likewise with fcr.
+ * The largest intermediate is 2^28 for both depths. */
+int uav_clip_to_yuv420_sited(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
+                             int32_t depth, const int32_t* coefs, void* stream);
 
 #ifdef __cplusplus
 }

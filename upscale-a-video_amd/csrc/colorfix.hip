@@ -557,6 +557,203 @@ __global__ __launch_bounds__(256) void clip_window_to_yuv_kernel(const float* __
     }
 }
 
+// ---- siting-aware 4:2:0 (uav_yuv420_sited_to_clip_f32 / uav_clip_to_yuv420_sited): `--chroma sited` of the front end ----------
+// Decode: bilinear chroma up-sampling at the siting of the input's tag instead of replication.  Per axis a luma sample takes two
+// chroma taps with weights in quarters — centre: (1,3) on c[i-1], c[i] for an even index, (3,1) on c[i], c[i+1] for an odd one;
+// co-sited: (0,4) and (2,2) — indices clamped to the plane; the axes multiply (sixteenths) and the colour conversion rounds once.
+struct YuvSiting { int he0, he1, ho0, ho1, ve0, ve1, vo0, vo1; };              // horizontal / vertical, even / odd index, tap 0 / 1
+
+UAV_DEVINL void yuv_to_rgb16(const YuvInv& k, int yy, int u16, int v16, float& r, float& g, float& b) {
+    const int y = (yy - k.yo) * k.iy * 16;
+    r = yuv_u8_to_clip(yuv_clamp255((y + k.rcr * v16 + (1 << 19)) >> 20));
+    g = yuv_u8_to_clip(yuv_clamp255((y + k.gcb * u16 + k.gcr * v16 + (1 << 19)) >> 20));
+    b = yuv_u8_to_clip(yuv_clamp255((y + k.bcb * u16 + (1 << 19)) >> 20));
+}
+
+// planes Y (T,H,W), Cb / Cr (T,ch,cw) [ch = ceil(H/2), cw = ceil(W/2)] -> clip (3,T,H,W) fp32.  Ownership and MODEs of
+// yuv_to_clip_kernel; a thread reads, beside its chroma word, the sample on either side of it in the rows ry-1, ry, ry+1
+// (6 samples x 3 rows per plane, clamped at the borders): re-reads of what its neighbours own.
+template <int MODE>
+__global__ __launch_bounds__(256) void yuv_sited_to_clip_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ cbp,
+                                                                const unsigned char* __restrict__ crp, float* __restrict__ dst, int t_len,
+                                                                int h, int w, YuvInv k, YuvSiting s) {
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = (h + 1) / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int rows = min(2, h - y0), n = min(YUV_RUN, w - x0);
+    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
+    const long long hw = (long long)h * w;
+    const unsigned char* ysrc = yp + ((long long)t * h + y0) * w + x0;
+    float* out = dst + ((long long)t * h + y0) * w + x0;                       // channel stride: t_len * hw
+    const long long cs = (long long)t_len * hw;
+    const long long crow[3] = {((long long)t * ch + max(ry - 1, 0)) * cw, ((long long)t * ch + ry) * cw,
+                               ((long long)t * ch + min(ry + 1, ch - 1)) * cw};
+    if (MODE > 0 && n == YUV_RUN) {
+        const int i0 = x0 >> 1, il = max(i0 - 1, 0), ir = min(i0 + 4, cw - 1);  // i0 + 3 <= cw - 1: the run is whole
+        int cbs[3][6], crs[3][6];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const unsigned char* pb = cbp + crow[a];
+            const unsigned char* pr = crp + crow[a];
+            uint32_t bw, rw;
+            if (MODE == 2) {
+                bw = *reinterpret_cast<const uint32_t*>(pb + i0);
+                rw = *reinterpret_cast<const uint32_t*>(pr + i0);
+            } else {
+                const unsigned short* hb = reinterpret_cast<const unsigned short*>(pb + i0);
+                const unsigned short* hr = reinterpret_cast<const unsigned short*>(pr + i0);
+                bw = (uint32_t)hb[0] | ((uint32_t)hb[1] << 16);
+                rw = (uint32_t)hr[0] | ((uint32_t)hr[1] << 16);
+            }
+            cbs[a][0] = pb[il]; crs[a][0] = pr[il];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cbs[a][1 + j] = (int)yuv_byte(bw, j); crs[a][1 + j] = (int)yuv_byte(rw, j); }
+            cbs[a][5] = pb[ir]; crs[a][5] = pr[ir];
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r >= rows) break;
+            uint32_t yw[2];
+            if (MODE == 2) {
+                const uint2_t v = *reinterpret_cast<const uint2_t*>(ysrc + (long long)r * w);
+                yw[0] = v.x; yw[1] = v.y;
+            } else {
+                yw[0] = *reinterpret_cast<const uint32_t*>(ysrc + (long long)r * w);
+                yw[1] = *reinterpret_cast<const uint32_t*>(ysrc + (long long)r * w + 4);
+            }
+            const int wa = r ? s.vo0 : s.ve0, wb = r ? s.vo1 : s.ve1;           // rows (ry-1, ry) for the even row, (ry, ry+1) for the odd one
+            int ub[6], vb[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) { ub[c] = wa * cbs[r][c] + wb * cbs[r + 1][c]; vb[c] = wa * crs[r][c] + wb * crs[r + 1][c]; }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {                                       // 4 pixels = one 16-byte store per channel
+                float4_t R, G, B;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = q * 4 + j, c = (px >> 1) + 1;                // samples (c-1, c) for an even pixel, (c, c+1) for an odd one
+                    const int u16 = ((px & 1) ? s.ho0 * ub[c] + s.ho1 * ub[c + 1] : s.he0 * ub[c - 1] + s.he1 * ub[c]) - 2048;
+                    const int v16 = ((px & 1) ? s.ho0 * vb[c] + s.ho1 * vb[c + 1] : s.he0 * vb[c - 1] + s.he1 * vb[c]) - 2048;
+                    float fr, fg, fb;
+                    yuv_to_rgb16(k, (int)yuv_byte(yw[q], j), u16, v16, fr, fg, fb);
+                    R[j] = fr; G[j] = fg; B[j] = fb;
+                }
+                float* o = out + (long long)r * w + q * 4;
+                *reinterpret_cast<float4_t*>(o) = R;
+                *reinterpret_cast<float4_t*>(o + cs) = G;
+                *reinterpret_cast<float4_t*>(o + 2 * cs) = B;
+            }
+        }
+        return;
+    }
+    for (int r = 0; r < rows; ++r) {
+        const long long ra = r ? crow[1] : crow[0], rb = r ? crow[2] : crow[1];
+        const int wa = r ? s.vo0 : s.ve0, wb = r ? s.vo1 : s.ve1;
+        for (int j = 0; j < n; ++j) {
+            const int x = x0 + j, ci = x >> 1;
+            const int ia = (x & 1) ? ci : max(ci - 1, 0), ib = (x & 1) ? min(ci + 1, cw - 1) : ci;
+            const int w0 = (x & 1) ? s.ho0 : s.he0, w1 = (x & 1) ? s.ho1 : s.he1;
+            const int u16 = wa * (w0 * cbp[ra + ia] + w1 * cbp[ra + ib]) + wb * (w0 * cbp[rb + ia] + w1 * cbp[rb + ib]) - 2048;
+            const int v16 = wa * (w0 * crp[ra + ia] + w1 * crp[ra + ib]) + wb * (w0 * crp[rb + ia] + w1 * crp[rb + ib]) - 2048;
+            float fr, fg, fb;
+            yuv_to_rgb16(k, ysrc[(long long)r * w + j], u16, v16, fr, fg, fb);
+            float* o = out + (long long)r * w + j;
+            o[0] = fr; o[cs] = fg; o[2 * cs] = fb;
+        }
+    }
+}
+
+// Encode, horizontally co-sited and vertically centred (the siting of `C420mpeg2` and `C420p10`): a chroma sample is made from
+// the (1,2,1) filter around its EVEN luma column in both rows of its block, weights totalling 8, one rounding.
+template <bool D10> UAV_DEVINL int yuv_chroma8(const int* f, int r, int g, int b) {
+    return yuv_clampd<D10>(((f[0] * r + f[1] * g + f[2] * b + (1 << 18)) >> 19) + YuvDepth<D10>::centre);
+}
+
+// frames (T,3,H,W) fp32 in [-1,1], H and W even -> planes Y (T,H,W), Cb / Cr (T,H/2,W/2), contiguous.  Ownership and MODEs of
+// clip_window_to_yuv_kernel; a thread reads one more column, x0 - 1 (clamped to the frame), per row and channel.
+template <int MODE, bool D10>
+__global__ __launch_bounds__(256) void clip_to_yuv420_sited_kernel(const float* __restrict__ src, void* __restrict__ yv, void* __restrict__ cbv,
+                                                                   void* __restrict__ crv, int h, int w, YuvFwd k) {
+    typedef typename YuvDepth<D10>::sample S;
+    constexpr int SB = (int)sizeof(S);
+    const int nrx = (w + YUV_RUN - 1) / YUV_RUN, nry = h / 2, cw = w / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nrx * nry) return;
+    const int t = blockIdx.y, ry = (int)(i / nrx), x0 = (int)(i - (long long)ry * nrx) * YUV_RUN, y0 = ry * 2;
+    const int n = min(YUV_RUN, w - x0);                                         // even
+    const long long hw = (long long)h * w;
+    const float* in = src + (long long)t * 3 * hw + (long long)y0 * w + x0;    // channel stride: hw
+    S* yd = reinterpret_cast<S*>(yv) + (long long)t * hw + (long long)y0 * w + x0;
+    const long long co = ((long long)t * nry + ry) * cw + (x0 >> 1);
+    S* cbd = reinterpret_cast<S*>(cbv) + co;
+    S* crd = reinterpret_cast<S*>(crv) + co;
+    if (MODE > 0 && n == YUV_RUN) {
+        constexpr int NW = YUV_RUN * SB / 4;                                    // 32-bit words of a run's luma samples of one row
+        const int back = x0 > 0 ? 1 : 0;
+        int sr[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint32_t yw[NW];
+#pragma unroll
+            for (int q = 0; q < NW; ++q) yw[q] = 0;
+            const float* p0 = in + (long long)r * w;
+            int pr = yuv_quant<D10>(p0[-back]), pg = yuv_quant<D10>(p0[hw - back]), pb = yuv_quant<D10>(p0[2 * hw - back]);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const float* p = p0 + q * 4;
+                const float4_t R = *reinterpret_cast<const float4_t*>(p);
+                const float4_t G = *reinterpret_cast<const float4_t*>(p + hw);
+                const float4_t B = *reinterpret_cast<const float4_t*>(p + 2 * hw);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = q * 4 + j;
+                    const int ir = yuv_quant<D10>(R[j]), ig = yuv_quant<D10>(G[j]), ib = yuv_quant<D10>(B[j]);
+                    yuv_pack<SB>(yw, px, yuv_luma_d<D10>(k, ir, ig, ib));
+                    if (px & 1) { sr[px >> 1] += ir; sg[px >> 1] += ig; sb[px >> 1] += ib; }
+                    else { sr[px >> 1] += pr + 2 * ir; sg[px >> 1] += pg + 2 * ig; sb[px >> 1] += pb + 2 * ib; }
+                    pr = ir; pg = ig; pb = ib;
+                }
+            }
+            yuv_store_run<MODE, YUV_RUN * SB>(yd + (long long)r * w, yw);
+        }
+        uint32_t bw[2] = {0, 0}, rw[2] = {0, 0};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            yuv_pack<SB>(bw, c, yuv_chroma8<D10>(k.fcb, sr[c], sg[c], sb[c]));
+            yuv_pack<SB>(rw, c, yuv_chroma8<D10>(k.fcr, sr[c], sg[c], sb[c]));
+        }
+        if constexpr (SB == 2) {
+            yuv_store_run<MODE, 8>(cbd, bw);
+            yuv_store_run<MODE, 8>(crd, rw);
+        } else if constexpr (MODE == 2) {
+            yuv_store<4>(cbd, bw);
+            yuv_store<4>(crd, rw);
+        } else {
+            unsigned short* a = reinterpret_cast<unsigned short*>(cbd);
+            unsigned short* b = reinterpret_cast<unsigned short*>(crd);
+            a[0] = (unsigned short)bw[0]; a[1] = (unsigned short)(bw[0] >> 16);
+            b[0] = (unsigned short)rw[0]; b[1] = (unsigned short)(rw[0] >> 16);
+        }
+        return;
+    }
+    for (int c = 0; c < n / 2; ++c) {                                           // one chroma sample and its 2x2 luma block at a time
+        const int back = x0 + c * 2 > 0 ? 1 : 0;
+        int s_r = 0, s_g = 0, s_b = 0;
+        for (int r = 0; r < 2; ++r) {
+            const float* p = in + (long long)r * w + c * 2;
+            const int r0 = yuv_quant<D10>(p[0]), g0 = yuv_quant<D10>(p[hw]), b0 = yuv_quant<D10>(p[2 * hw]);
+            const int r1 = yuv_quant<D10>(p[1]), g1 = yuv_quant<D10>(p[hw + 1]), b1 = yuv_quant<D10>(p[2 * hw + 1]);
+            yd[(long long)r * w + c * 2] = (S)yuv_luma_d<D10>(k, r0, g0, b0);
+            yd[(long long)r * w + c * 2 + 1] = (S)yuv_luma_d<D10>(k, r1, g1, b1);
+            s_r += yuv_quant<D10>(p[-back]) + 2 * r0 + r1;
+            s_g += yuv_quant<D10>(p[hw - back]) + 2 * g0 + g1;
+            s_b += yuv_quant<D10>(p[2 * hw - back]) + 2 * b0 + b1;
+        }
+        cbd[c] = (S)yuv_chroma8<D10>(k.fcb, s_r, s_g, s_b);
+        crd[c] = (S)yuv_chroma8<D10>(k.fcr, s_r, s_g, s_b);
+    }
+}
+
 inline bool yuv_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline int yuv_mode(int w, const void* f32, const void* y, const void* cb, const void* cr, bool c444) {
     if (!yuv_aligned(f32, 16)) return 0;
@@ -689,6 +886,62 @@ extern "C" int uav_clip_window_to_yuv(const float* src, int64_t src_c_stride, in
     if (depth == 8) clip_window_to_yuv_launch<true, false>(mode, grid, s, src, y, cb, cr, h, w, g, k);
     else if (chroma444) clip_window_to_yuv_launch<true, true>(mode, grid, s, src, y, cb, cr, h, w, g, k);
     else clip_window_to_yuv_launch<false, true>(mode, grid, s, src, y, cb, cr, h, w, g, k);
+    return uav_launch_status();
+}
+
+extern "C" int uav_yuv420_sited_to_clip_f32(const void* y, const void* cb, const void* cr, float* clip_cthw, int32_t t_len, int32_t h,
+                                            int32_t w, int32_t centre_h, int32_t centre_v, const int32_t* coefs, void* stream) {
+    if (!y || !cb || !cr || !clip_cthw || !coefs) return UAV_EINVAL;
+    if ((centre_h != 0 && centre_h != 1) || (centre_v != 0 && centre_v != 1)) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0) return UAV_ESHAPE;
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * ((h + 1) / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    const YuvInv k = {coefs[0], coefs[1], coefs[2], coefs[3], coefs[4], coefs[5]};
+    YuvSiting s;
+    s.he0 = centre_h ? 1 : 0; s.he1 = centre_h ? 3 : 4; s.ho0 = centre_h ? 3 : 2; s.ho1 = centre_h ? 1 : 2;
+    s.ve0 = centre_v ? 1 : 0; s.ve1 = centre_v ? 3 : 4; s.vo0 = centre_v ? 3 : 2; s.vo1 = centre_v ? 1 : 2;
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    const unsigned char *yp = (const unsigned char*)y, *cbp = (const unsigned char*)cb, *crp = (const unsigned char*)cr;
+    switch (yuv_mode(w, clip_cthw, y, cb, cr, false)) {
+    case 2: hipLaunchKernelGGL(yuv_sited_to_clip_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip_cthw, t_len, h, w, k, s); break;
+    case 1: hipLaunchKernelGGL(yuv_sited_to_clip_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip_cthw, t_len, h, w, k, s); break;
+    default: hipLaunchKernelGGL(yuv_sited_to_clip_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, clip_cthw, t_len, h, w, k, s);
+    }
+    return uav_launch_status();
+}
+
+namespace {
+template <bool D10>
+void clip_to_yuv420_sited_launch(int mode, dim3 grid, hipStream_t s, const float* src, void* y, void* cb, void* cr, int h, int w,
+                                 const YuvFwd& k) {
+    switch (mode) {
+    case 2: hipLaunchKernelGGL((clip_to_yuv420_sited_kernel<2, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, k); break;
+    case 1: hipLaunchKernelGGL((clip_to_yuv420_sited_kernel<1, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, k); break;
+    default: hipLaunchKernelGGL((clip_to_yuv420_sited_kernel<0, D10>), grid, dim3(256), 0, s, src, y, cb, cr, h, w, k);
+    }
+}
+}  // namespace
+
+extern "C" int uav_clip_to_yuv420_sited(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
+                                        int32_t depth, const int32_t* coefs, void* stream) {
+    if (!frames_tchw || !y || !cb || !cr || !coefs) return UAV_EINVAL;
+    if (depth != 8 && depth != 10) return UAV_EINVAL;
+    if (t_len <= 0 || t_len > 65535 || h <= 0 || w <= 0 || (h & 1) || (w & 1)) return UAV_ESHAPE;
+    const uintptr_t sb = depth == 10 ? 2 : 1;                                   // bytes per sample
+    if (!yuv_aligned(y, sb) || !yuv_aligned(cb, sb) || !yuv_aligned(cr, sb)) return UAV_EALIGN;
+    const long long threads = (long long)((w + YUV_RUN - 1) / YUV_RUN) * (h / 2), blocks = (threads + 255) / 256;
+    if (blocks >= (1ll << 31)) return UAV_ESHAPE;
+    YuvFwd k;
+    for (int i = 0; i < 3; ++i) { k.fy[i] = coefs[i]; k.fcb[i] = coefs[3 + i]; k.fcr[i] = coefs[6 + i]; }
+    k.yo = coefs[9];
+    // contiguous planes: rows and frames keep the alignment of the bases when w allows the mode at all
+    const auto planes_ok = [&](uintptr_t a) {
+        return w % (int)a == 0 && yuv_aligned(y, a * sb) && yuv_aligned(cb, a / 2 * sb) && yuv_aligned(cr, a / 2 * sb);
+    };
+    const int mode = !yuv_aligned(frames_tchw, 16) ? 0 : planes_ok(8) ? 2 : planes_ok(4) ? 1 : 0;
+    const dim3 grid((unsigned)blocks, (unsigned)t_len);
+    if (depth == 10) clip_to_yuv420_sited_launch<true>(mode, grid, (hipStream_t)stream, frames_tchw, y, cb, cr, h, w, k);
+    else clip_to_yuv420_sited_launch<false>(mode, grid, (hipStream_t)stream, frames_tchw, y, cb, cr, h, w, k);
     return uav_launch_status();
 }
 

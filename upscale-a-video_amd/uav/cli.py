@@ -19,7 +19,10 @@ Input stays 8-bit.  `--out-size WxH` (or `W:H`) or `--out-scale S` (1 to 4) writ
 size up to 4x of it: 480p material at 1080p is `--out-scale 2.25`.  Each chunk's fp32 frames are resized on the GPU with an
 antialiased cubic filter (`uav_resize_aa_f32`: the filter of `F.interpolate(mode='bicubic', antialias=True)`, after the colour
 fix and before the colour conversion), so only frames of the delivery size reach the host; `--matrix auto` goes by the rows
-written.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
+written.  `--chroma sited` filters 4:2:0 chroma at the position the tags declare instead of replicating samples on the way in and
+writing block means on the way out: bilinear up-sampling at the input tag's siting (`uav_yuv420_sited_to_clip_f32`) and, for the
+left-sited tags written (`C420mpeg2`, `C420p10`), a (1,2,1) filter around the even column (`uav_clip_to_yuv420_sited`); the default,
+`replicate`, keeps every file's bytes as they were.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
 each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
 caption text, default none.
 
@@ -83,6 +86,9 @@ def build_parser():
                    help="size of the frames written (also W:H), from the network's input size up to 4x of it; default 4x")
     p.add_argument("--out-scale", dest="out_scale", metavar="S", default=None,
                    help="the same as a factor of the network's input size, 1 to 4 (2.25: 480p -> 1080p); sides are rounded to even")
+    p.add_argument("--chroma", default="replicate", choices=["replicate", "sited"],
+                   help="4:2:0 chroma: replicate = samples replicated on input, block means on output (default, the files' bytes as "
+                        "ever); sited = filtered at the position the Y4M tags declare, on both sides")
     p.add_argument("--seed", type=int, default=10)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
@@ -223,7 +229,7 @@ def run(args):
         out_h, out_w = _output_size(source, size, scale, fmt)
         name = "stdin" if path == "-" else os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
         if isinstance(source, video_io.Y4MClip):
-            clip = video_io.preprocess_planes(source, device, args.matrix)
+            clip = video_io.preprocess_planes(source, device, args.matrix, chroma=args.chroma)
             in_size = source.size
         else:
             frames = torch.from_numpy(source).permute(0, 3, 1, 2).contiguous()
@@ -253,7 +259,7 @@ def run(args):
                                               guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
                                               perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
                                               coefs=None if need_frames else coefs, fmt=fmt,
-                                              out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w))
+                                              out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w), chroma=args.chroma)
         with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, out_w, out_h, args.fps or fps or 24, full_range,
                                 fmt) as out:
             for chunk in chunks:                                # one chunk is alive: decoded, converted and written before the next
@@ -263,7 +269,7 @@ def run(args):
                         _save_png(rgb, os.path.join(args.output_path, "frame", save_name), first=out.frames)
                     if dump is not None:
                         dump.append(rgb)
-                    chunk = video_io.postprocess_planes(chunk, coefs, fmt)
+                    chunk = video_io.postprocess_planes(chunk, coefs, fmt, video_io.output_siting(fmt, full_range, args.chroma))
                 out.write(*chunk)
                 del chunk                                       # before the generator decodes the next one
         if device.type == "cuda":

@@ -1444,3 +1444,54 @@ def clip_window_to_yuv(window, y, cb, cr, coefs, *, chroma444, depth, frames_fir
     rc = lib.uav_clip_window_to_yuv(_p(window), window.stride(c_dim), window.stride(t_dim), window.stride(2), _p(y), pitch(y), y.stride(0),
                                     _p(cb), _p(cr), pitch(cb), cb.stride(0), t, h, w, int(bool(chroma444)), depth, k, _stream())
     _lib.check(rc, "uav_clip_window_to_yuv")
+
+
+def yuv420_sited_to_clip_f32(y, cb, cr, coefs, siting):
+    """`yuv420_to_clip_f32` for 4:2:0 planes with bilinear chroma up-sampling at the siting the input declares instead of
+    replication: `siting` = (centre_h, centre_v), each True when the chroma sample lies between its two luma samples on that axis
+    and False when it lies on the even one (`video_io.chroma_siting(tag)`).  One pass, one rounding (`uav_yuv420_sited_to_clip_f32`)."""
+    lib = _lib.load()
+    for name, p in (("y", y), ("cb", cb), ("cr", cr)):
+        _req(p, torch.uint8, name)
+        if p.dim() != 3 or p.device != y.device:
+            raise _lib.UavError(f"yuv420_sited_to_clip_f32: {name} must be a (T,H,W) plane stack on one device")
+    try:
+        centre_h, centre_v = siting
+    except (TypeError, ValueError):
+        centre_h = centre_v = None
+    if centre_h not in (False, True, 0, 1) or centre_v not in (False, True, 0, 1):
+        raise _lib.UavError(f"yuv420_sited_to_clip_f32: siting must be (centre_h, centre_v) of booleans, got {siting!r} (UAV_EINVAL)")
+    t, h, w = y.shape
+    cshape = (t, (h + 1) // 2, (w + 1) // 2)
+    if tuple(cb.shape) != cshape or tuple(cr.shape) != cshape:
+        raise _lib.UavError(f"yuv420_sited_to_clip_f32: chroma planes {tuple(cb.shape)} / {tuple(cr.shape)}, expected {cshape}")
+    k = _coef_array(coefs.inverse, 6, "yuv420_sited_to_clip_f32")
+    out = torch.empty((3, t, h, w), dtype=torch.float32, device=y.device)
+    rc = lib.uav_yuv420_sited_to_clip_f32(_p(y), _p(cb), _p(cr), _p(out), t, h, w, int(bool(centre_h)), int(bool(centre_v)), k, _stream())
+    _lib.check(rc, "uav_yuv420_sited_to_clip_f32")
+    return out
+
+
+def clip_to_yuv420_sited(frames, coefs, depth=8):
+    """(T,3,H,W) fp32 in [-1,1], H and W even -> 4:2:0 planes Y (T,H,W), Cb, Cr (T,H/2,W/2) whose chroma is horizontally co-sited
+    and vertically centred (the siting of the `C420mpeg2` and `C420p10` tags): the (1,2,1) filter around the even column over both
+    rows of a block, one rounding.  `depth` 8 (uint8 planes, the luma of `clip_to_yuv420_u8`) or 10 (int16 planes holding 0..1023,
+    the luma of `clip_window_to_yuv`); `coefs` of that depth.  One pass (`uav_clip_to_yuv420_sited`)."""
+    lib = _lib.load()
+    if depth not in (8, 10):
+        raise _lib.UavError(f"clip_to_yuv420_sited: depth 8 or 10 expected, got {depth!r} (UAV_EINVAL)")
+    _req(frames, torch.float32, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise _lib.UavError("clip_to_yuv420_sited: (T,3,H,W) fp32 expected")
+    t, _, h, w = frames.shape
+    if h % 2 or w % 2:
+        raise _lib.UavError(f"clip_to_yuv420_sited: H and W must be even for 4:2:0 planes, got {h}x{w} (UAV_ESHAPE)")
+    if getattr(coefs, "depth", 8) != depth:
+        raise _lib.UavError(f"clip_to_yuv420_sited: coefficients of depth {getattr(coefs, 'depth', 8)} for planes of depth {depth}")
+    k = _coef_array(coefs.forward, 10, "clip_to_yuv420_sited")
+    sample = torch.uint8 if depth == 8 else torch.int16
+    y = torch.empty((t, h, w), dtype=sample, device=frames.device)
+    cb = torch.empty((t, h // 2, w // 2), dtype=sample, device=frames.device)
+    cr = torch.empty_like(cb)
+    _lib.check(lib.uav_clip_to_yuv420_sited(_p(frames), _p(y), _p(cb), _p(cr), t, h, w, depth, k, _stream()), "uav_clip_to_yuv420_sited")
+    return y, cb, cr

@@ -22,6 +22,12 @@ Output size: the network's result is 4x its input; `output_size` turns the progr
 antialiased cubic filter of `ops.resize_aa_f32` (csrc/resize_aa.hip) before they are converted, so nothing larger than the
 delivery size crosses to the host.
 
+Chroma siting: by default (`chroma="replicate"`) a 4:2:0 chroma sample is replicated over its 2x2 block on the way in and is the
+block's mean on the way out, whatever the tag says — the bytes of the program's files are pinned by tests, so that stays the
+default.  `chroma="sited"` (`--chroma sited`) filters at the position the tags declare: bilinear up-sampling at `chroma_siting(tag)`
+on the way in (`uav_yuv420_sited_to_clip_f32`) and, for the left-sited tags written (`C420mpeg2`, `C420p10`), the (1,2,1) filter
+around the even column on the way out (`uav_clip_to_yuv420_sited`).
+
 Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
 import os
@@ -64,6 +70,11 @@ def _plane_dtype(fmt: OutFormat):
 
 _KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 _CHROMA_420 = ("C420jpeg", "C420mpeg2", "C420paldv", "C420")
+CHROMA_MODES = ("replicate", "sited")
+# (centre_h, centre_v) per 4:2:0 tag: True when the chroma sample lies between its two luma samples on that axis, False when it
+# lies on the even one.  'C420paldv' is top-left, as ffmpeg maps it; 'C420p10' is what this program writes for 10 bits.
+_SITING = {"C420jpeg": (True, True), "C420mpeg2": (False, True), "C420": (False, True), "": (False, True), "C420p10": (False, True),
+           "C420paldv": (False, False)}
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
 
@@ -161,25 +172,63 @@ def output_size(h4: int, w4: int, *, out_size=None, out_scale=None, fmt):
     return h4, w4
 
 
-def preprocess_planes(clip: Y4MClip, device, matrix: str = "auto") -> torch.Tensor:
+def chroma_siting(tag: str):
+    """(centre_h, centre_v) of the chroma samples of a 4:2:0 Y4M colour-space tag ('' = no `C` tag): 'C420jpeg' centre / centre,
+    'C420mpeg2', 'C420' and no tag co-sited horizontally and centred vertically, 'C420paldv' co-sited on both axes (top-left, as
+    ffmpeg maps it); also 'C420p10', which is written left-sited like 'C420mpeg2'.  ValueError for any other tag."""
+    if tag not in _SITING:
+        raise ValueError(f"no 4:2:0 chroma siting is known for the tag {tag!r}")
+    return _SITING[tag]
+
+
+def _chroma_mode(chroma):
+    if chroma not in CHROMA_MODES:
+        raise ValueError(f"chroma must be one of {list(CHROMA_MODES)}, got {chroma!r}")
+    return chroma
+
+
+def output_siting(fmt, full_range: bool, chroma: str = "replicate"):
+    """The siting `postprocess_planes` is to filter for, given the tag `y4m_header` writes for `fmt` and the range: None — the
+    block-mean kernels, as ever — with `chroma="replicate"`, for the 4:4:4 formats (no filter) and for 'C420jpeg' (centre /
+    centre IS the block mean); `chroma_siting(tag)` = (False, True) for 'C420mpeg2' and 'C420p10'."""
+    fmt = out_format(fmt)
+    if _chroma_mode(chroma) == "replicate" or fmt.chroma444:
+        return None
+    siting = chroma_siting(fmt.tag or ("C420jpeg" if full_range else "C420mpeg2"))
+    return None if siting == (True, True) else siting
+
+
+def preprocess_planes(clip: Y4MClip, device, matrix: str = "auto", chroma: str = "replicate") -> torch.Tensor:
     """A decoded .y4m clip -> (1,3,T,h,w) fp32 in [-1,1] on `device`: what `preprocess_frames` returns for the uint8 RGB
     frames a decoder with the fixed-point arithmetic of `uav_yuv420_to_clip_f32` would have produced (colour conversion
-    and normalisation are one pass over 1.5 bytes per pixel; the >= 1280-px area pooling follows as there)."""
+    and normalisation are one pass over 1.5 bytes per pixel; the >= 1280-px area pooling follows as there).
+    `chroma="sited"`: 4:2:0 chroma is up-sampled bilinearly at `chroma_siting(clip.colorspace)` in the same pass
+    (`ops.yuv420_sited_to_clip_f32`) instead of being replicated; 'C444' input has nothing to up-sample and ignores the option."""
     coefs = yuv_coefficients(auto_matrix(clip.size[0]) if matrix == "auto" else matrix, clip.full_range)
+    sited = _chroma_mode(chroma) == "sited" and clip.colorspace != "C444"
     y, cb, cr = (torch.from_numpy(p).to(device) for p in (clip.y, clip.cb, clip.cr))
     with E.device_guard(y):
-        out = ops.yuv420_to_clip_f32(y, cb, cr, coefs, chroma444=clip.colorspace == "C444")
+        if sited:
+            out = ops.yuv420_sited_to_clip_f32(y, cb, cr, coefs, chroma_siting(clip.colorspace))
+        else:
+            out = ops.yuv420_to_clip_f32(y, cb, cr, coefs, chroma444=clip.colorspace == "C444")
         return _pool_large(out).unsqueeze(0)
 
 
-def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs, fmt="420"):
+def postprocess_planes(output: torch.Tensor, coefs: YuvCoefs, fmt="420", siting=None):
     """(T,3,H,W) in [-1,1] -> uint8 planes Y (T,H,W), Cb, Cr (T,H/2,W/2) on the device: `postprocess_frames`' uint8 RGB value,
     converted and 2x2-averaged in the same pass (reads the fp32 frames once, writes 1.5 bytes per pixel).  With another `fmt`
     of `OUT_FORMATS`: the planes of that format — Cb, Cr (T,H,W) for 4:4:4, int16 holding 0..1023 for 10 bits — in one pass too;
-    `coefs` must be of the format's depth."""
+    `coefs` must be of the format's depth.  `siting` = (centre_h, centre_v) of the chroma samples to make (`output_siting`): None
+    or (True, True) is the block mean above; (False, True), for a 4:2:0 format, is `ops.clip_to_yuv420_sited` — same luma,
+    chroma filtered around the even column; a 4:4:4 format has no chroma filter and ignores it."""
     fmt = out_format(fmt)
+    if siting is not None and tuple(siting) not in ((True, True), (False, True)):
+        raise ValueError(f"output chroma is written centre / centre or left-sited (False, True), got siting {siting!r}")
     with E.device_guard(output):
         frames = output.float().contiguous()
+        if siting is not None and tuple(siting) == (False, True) and not fmt.chroma444:
+            return ops.clip_to_yuv420_sited(frames, coefs, fmt.depth)
         if fmt.name == "420":
             return ops.clip_to_yuv420_u8(frames, coefs)
         t, _, h, w = frames.shape
@@ -202,8 +251,8 @@ def _new_planes(like, t, h, w, fmt: OutFormat):
 def read_y4m(path) -> Y4MClip:
     """Read a progressive 8-bit YUV4MPEG2 file — `path`, or an open binary stream such as a pipe, named by its `.name` in
     messages — whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
-    (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is ignored: every 4:2:0 flavour is up-sampled by replicating
-    a sample over its 2x2 block.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
+    (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is not applied here: the tag is kept in `colorspace`, and
+    `preprocess_planes` replicates a sample over its 2x2 block by default or, with `chroma="sited"`, filters at `chroma_siting(tag)`.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
     rest.  Anything else (4:2:2, mono, more than 8 bits, interlaced, a truncated frame) raises ValueError naming the tag."""
     import numpy as np
     if hasattr(path, "read"):
@@ -401,7 +450,7 @@ def _window_to_planes(window, planes, dst, coefs, fmt=OUT_FORMATS["420"]):
 
 def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
                         noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None, fmt="420",
-                        out_size=None):
+                        out_size=None, chroma="replicate"):
     """What the upscaling program does with one video between reading and writing it, in its order, 3 output frames at a time:
     bidirectional flows of the whole clip when propagation steps are asked for, then the DDIM loop of the whole clip — of
     every tile (`tiling.needs_tiling`: asked for, or h*w >= 384*384), or of the one pipeline call — whose results live at the
@@ -415,12 +464,18 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     colour fix's branch; resampling crosses tile borders, so the tile-by-tile conversion cannot serve), colour-fixed at 4x when
     asked, resized to (n,3,H,W) with `ops.resize_aa_f32` and converted then.  That costs, per chunk of 3 frames and beside the
     decoder's output, the fp32 frames at 4x (3*3*4h*4w*4 bytes), the resizer's intermediate (3*3*4h*W*4) and its result
-    (3*3*H*W*4).  `None` or (4h, 4w): today's path, unchanged."""
+    (3*3*H*W*4).  `None` or (4h, 4w): today's path, unchanged.
+
+    `chroma="sited"` with `coefs` of a left-sited 4:2:0 output (`output_siting(fmt, coefs.full_range, chroma)`): the 3-tap
+    chroma filter crosses tile borders, so a chunk is assembled as fp32 frames too (the same branch) and converted by
+    `postprocess_planes(..., siting=...)`.  Every other case — 'replicate', 4:4:4, full-range 8-bit 4:2:0 — is unchanged."""
     from models_video import color_correction
     from . import tiling
     if color_fix not in ("None", "AdaIn", "Wavelet"):
         raise ValueError(f"color_fix must be 'None', 'AdaIn' or 'Wavelet', got {color_fix!r}")
     fmt = out_format(fmt)
+    _chroma_mode(chroma)
+    siting = output_siting(fmt, coefs.full_range, chroma) if coefs is not None else None      # fp32 frames have no chroma planes
     propagation_steps = list(propagation_steps)
     if propagation_steps and raft is None:
         raise ValueError("propagation steps need a flow estimator (raft=...)")
@@ -441,7 +496,7 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     for start, n, pieces in chunks:
         with torch.no_grad(), E.device_guard(clip):
             window = None
-            if coefs is not None and color_fix == "None" and out_size is None:
+            if coefs is not None and color_fix == "None" and out_size is None and siting is None:
                 out = _new_planes(clip, n, 4 * h, 4 * w, fmt)
                 for dst, window in pieces:
                     _window_to_planes(window, out, dst, coefs, fmt)
@@ -459,7 +514,7 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
                 if out_size is not None:
                     out = ops.resize_aa_f32(out.contiguous(), *out_size)
                 if coefs is not None:
-                    out = postprocess_planes(out, coefs, fmt)
+                    out = postprocess_planes(out, coefs, fmt, siting)
             del pieces, window                                  # views of the decoder's output: let it go before the next decode
         yield out
         del out
