@@ -23,16 +23,18 @@ __global__ __launch_bounds__(256) void plane_partial_kernel(const float* __restr
     long long i1 = i0 + per; if (i1 > hw) i1 = hw;
     const float* p = x + (long long)plane * hw;
     double s = 0.0, q = 0.0;
-    // fp32 running sums over short strips (<= 64 elements), folded into fp64: keeps the 1.6 M-element reduction exact
-    // to ~1e-7 relative without paying fp64 per element
-    for (long long i = i0 + tid; i < i1; i += 256 * 64) {
-        float fs = 0.f, fq = 0.f;
-#pragma unroll 8
-        for (int u = 0; u < 64; ++u) {
+    // fp64 sums of the values and of their squares (the square of an fp32 number is exact in fp64): the variance is
+    // q - n m^2, which cancels all but var / mean^2 of q, so a square rounded to fp32 would cost a near-constant plane
+    // most of its variance.  8 independent loads are in flight per thread.
+    for (long long i = i0 + tid; i < i1; i += 256 * 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
             const long long j = i + (long long)u * 256;
-            if (j < i1) { const float v = p[j]; fs += v; fq += v * v; }
+            v[u] = j < i1 ? p[j] : 0.f;
         }
-        s += fs; q += fq;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const double d = (double)v[u]; s += d; q += d * d; }
     }
     rs[tid] = s; rq[tid] = q;
     __syncthreads();
