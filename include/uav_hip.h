@@ -585,7 +585,9 @@ int uav_clip_window_to_yuv420_u8(const float* src, int64_t src_c_stride, int64_t
  * coefs = {fy[3], fcb[3], fcr[3], yo} for both depths (uav.video_io.yuv_coefficients(matrix, full_range, depth).forward); the
  * chroma centre C and the largest sample M follow from `depth`: C = 128, M = 255 for 8, C = 512, M = 1023 for 10.
  *   depth 8:  (r, g, b) = the uint8 RGB value as uav_clip_to_frames_u8 forms it; the coefficients are those of
- *             uav_clip_to_yuv420_u8.  chroma444 = 0 IS uav_clip_window_to_yuv420_u8 (same kernels, same bytes).
+ *             uav_clip_to_yuv420_u8.  uav_clip_window_to_yuv420_u8 IS this entry point with chroma444 = 0 and depth = 8.
+ *   Every encoder — this one, uav_clip_to_yuv420_u8 and uav_clip_to_yuv420_sited, whose contiguous tensors are the window that
+ *   is the whole — launches one kernel, clip_to_yuv_kernel (csrc/yuv_io.hip): same bytes from each for the same format.
  *   depth 10: no 8-bit intermediate: v = clamp(x/2 + 0.5, 0, 1) in fp32, (r, g, b) = (int)(v * 4095.0f + 0.5f), 12-bit RGB;
  *             the coefficients are round(k * S / 4095 * 65536) with S = 1023 and yo = 0 for full range, S = 876 (luma) /
  *             896 (chroma) and yo = 64 for limited range.

@@ -1,4 +1,4 @@
-"""`--chroma sited` on the device: the two siting-aware 4:2:0 kernels (csrc/colorfix.hip K13: uav_yuv420_sited_to_clip_f32 /
+"""`--chroma sited` on the device: the two siting-aware 4:2:0 kernels (csrc/yuv_io.hip K13: uav_yuv420_sited_to_clip_f32 /
 uav_clip_to_yuv420_sited) against the numpy reference of tests/chroma_sited_ref.py — bit for bit, inside 4 KiB guards, at every
 alignment —, their argument checks, `preprocess_planes` / `postprocess_planes` against the direct ops, and the upscaling program
 (uav/cli.py) end to end."""

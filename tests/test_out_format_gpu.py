@@ -1,4 +1,4 @@
-"""The output formats beside 8-bit 4:2:0 on the device: `uav_clip_window_to_yuv` (csrc/colorfix.hip) against
+"""The output formats beside 8-bit 4:2:0 on the device: `uav_clip_window_to_yuv` (csrc/yuv_io.hip) against
 tests/yuv_fmt_ref.py, sample for sample, in every access mode and on every tail, with the bytes around the box and around the
 planes untouched; its refusals; and the program's files for `--out-format` against the reference's planes of
 `upscale_clip`'s fp32 frames."""
@@ -123,6 +123,38 @@ def test_444_luma_is_the_420_kernels_luma_and_depth_8_420_is_that_kernel(dev, ma
         same = [torch.zeros_like(p) for p in old]
         ops.clip_window_to_yuv(window, *same, coefs, chroma444=False, depth=8)
         assert all(torch.equal(a, b) for a, b in zip(same, old))
+
+
+def test_every_420_entry_point_shares_one_core(dev):
+    """Contiguous (T,3,H,W) frames at one thread scalar, a 2-pixel tail, the half-width mode with its scalar 4-pixel tail, and the
+    full-width mode: `uav_clip_to_yuv420_u8`, `uav_clip_window_to_yuv420_u8` and `uav_clip_window_to_yuv(0, 8)` write the same
+    planes, and the luma of `uav_clip_to_yuv420_sited` is the luma of the unsited entry of its depth."""
+    from uav import _lib, ops, video_io
+    lib = _lib.load()
+    for t, h, w in ((2, 2, 2), (1, 6, 10), (2, 4, 12), (1, 6, 24)):
+        frames = _values((t, 3, h, w), seed=t + h + w).to(dev)
+        for depth in (8, 10):
+            coefs = video_io.yuv_coefficients("bt709", False, depth=depth)
+            k = _coefs("bt709", False, depth)
+            dtype = torch.uint8 if depth == 8 else torch.int16
+
+            def planes():
+                return [torch.zeros((t, h, w), dtype=dtype, device=dev)] + [torch.zeros((t, h // 2, w // 2), dtype=dtype, device=dev) for _ in range(2)]
+
+            def geometry(p):                                                  # the contiguous tensors as a window
+                return (frames.data_ptr(), h * w, 3 * h * w, w, p[0].data_ptr(), w, h * w, p[1].data_ptr(), p[2].data_ptr(), w // 2, h * w // 4, t, h, w)
+            unsited = planes()
+            assert lib.uav_clip_window_to_yuv(*geometry(unsited), 0, depth, k, None) == 0
+            if depth == 8:
+                window = planes()
+                assert lib.uav_clip_window_to_yuv420_u8(*geometry(window), k, None) == 0
+                torch.cuda.synchronize()
+                contiguous = ops.clip_to_yuv420_u8(frames, coefs)
+                for a, b, c in zip(contiguous, window, unsited):
+                    assert torch.equal(a, c) and torch.equal(b, c), f"{(t, h, w)}: the 8-bit 4:2:0 entry points differ"
+            torch.cuda.synchronize()
+            sited = ops.clip_to_yuv420_sited(frames, coefs, depth=depth)
+            assert torch.equal(sited[0], unsited[0]), f"{(t, h, w)} depth {depth}: sited luma is not the unsited entry's"
 
 
 def test_ops_wrapper_takes_views_and_copies_nothing(dev):

@@ -1,4 +1,4 @@
-"""Streaming the 4x frames on the device: the window kernel (csrc/colorfix.hip `uav_clip_window_to_yuv420_u8`: a strided
+"""Streaming the 4x frames on the device: the window kernel (csrc/yuv_io.hip `uav_clip_window_to_yuv420_u8`: a strided
 crop of decoder output converted straight into a box of larger planes) against tests/yuv_ref.py — bit for bit, with the bytes
 around the box and around the planes untouched —, its refusals, the program's files against the whole-clip path restated by
 hand (the colour fixes applied to the WHOLE clip there, per chunk in the program), and the peak of device memory."""

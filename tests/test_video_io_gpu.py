@@ -1,4 +1,4 @@
-"""SURVEY §8 row f4, device side: the CLI's frame pre/post-processing as HIP kernels (uav/video_io.py, csrc/colorfix.hip K13)
+"""SURVEY §8 row f4, device side: the CLI's frame pre/post-processing as HIP kernels (uav/video_io.py, csrc/yuv_io.hip K13)
 against the CLI's own eager tensor ops (inference_upscale_a_video.py:180-187,357-359) — bit-exact."""
 import numpy as np
 import pytest

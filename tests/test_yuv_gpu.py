@@ -1,4 +1,4 @@
-"""The Y4M front end on the device: the two Y'CbCr kernels (csrc/colorfix.hip K13: uav_yuv420_to_clip_f32 /
+"""The Y4M front end on the device: the two Y'CbCr kernels (csrc/yuv_io.hip K13: uav_yuv420_to_clip_f32 /
 uav_yuv444_to_clip_f32 / uav_clip_to_yuv420_u8) against the numpy reference of tests/yuv_ref.py composed with the existing
 pre/post-processing — bit for bit —, their bounds behaviour, and the upscaling program (uav/cli.py) end to end."""
 import os

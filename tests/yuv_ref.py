@@ -1,4 +1,4 @@
-"""numpy reference of the two Y'CbCr conversions (csrc/colorfix.hip K13, include/uav_hip.h), on int64, written from the
+"""numpy reference of the two Y'CbCr conversions (csrc/yuv_io.hip K13, include/uav_hip.h), on int64, written from the
 formulas of the C ABI's documentation: shared by the CPU and GPU tests of the Y4M front end."""
 import numpy as np
 

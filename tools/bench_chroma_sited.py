@@ -1,7 +1,8 @@
-"""Same-process timing of the siting-aware 4:2:0 kernels of the Y4M front end (csrc/colorfix.hip K13, `--chroma sited`) against the
+"""Same-process timing of the siting-aware 4:2:0 kernels of the Y4M front end (csrc/yuv_io.hip K13, `--chroma sited`) against the
 kernels they stand beside, in the style of tools/bench_out_format.py.  The algorithmic bytes of each pair are equal:
   decode, planes (8,H,W) for 320x320 and 1280x1280:   uav_yuv420_sited_to_clip_f32  vs  uav_yuv420_to_clip_f32   (1.5 B read + 12 B written per pixel)
   encode 8-bit, frames (8,3,1280,1280):               uav_clip_to_yuv420_sited (8)  vs  uav_clip_to_yuv420_u8    (12 + 1.5)
+  encode 8-bit, frames (8,3,1280,1284), W % 8 == 4:   the same pair in the half-width mode (4-byte luma, 2-byte chroma stores)
   encode 10-bit, the same frames:                     uav_clip_to_yuv420_sited (10) vs  uav_clip_window_to_yuv 420p10 on contiguous frames (12 + 3)
 Per kernel: ROUNDS rounds, interleaved between all kernels, of 20 warm launches between two HIP events; the launches rotate over NBUF
 input tensors (4 x 157 MB of frames, more than the 256 MiB Infinity Cache; the 1280x1280 decoder writes 4 x 157 MB); the encoders'
@@ -79,6 +80,11 @@ def main():
              ("encode10", "uav_clip_window_to_yuv", "yardstick", (t, 3, h, w),
               lambda f: ops.clip_window_to_yuv(f, *p10, k10, chroma444=False, depth=10, frames_first=True), frames, 15.0),
              ("encode10", "uav_clip_to_yuv420_sited", "sited", (t, 3, h, w), lambda f: ops.clip_to_yuv420_sited(f, k10, 10), frames, 15.0)]
+    # W % 8 == 4: the half-width mode (4-byte luma and 2-byte chroma stores), which no 1280-wide frame takes
+    w4 = w + 4
+    frames4 = [(torch.randn(t, 3, h, w4, generator=g) * 0.8).to(dev) for _ in range(NBUF)]
+    cases += [("encode8_w1284", "uav_clip_to_yuv420_u8", "yardstick", (t, 3, h, w4), lambda f: ops.clip_to_yuv420_u8(f, k8), frames4, 13.5),
+              ("encode8_w1284", "uav_clip_to_yuv420_sited", "sited", (t, 3, h, w4), lambda f: ops.clip_to_yuv420_sited(f, k8, 8), frames4, 13.5)]
     for side in (320, 1280):
         planes = [tuple(torch.randint(0, 256, s, generator=g, dtype=torch.uint8).to(dev)
                         for s in ((t, side, side), (t, side // 2, side // 2), (t, side // 2, side // 2))) for _ in range(NBUF)]
@@ -103,7 +109,7 @@ def main():
                                      input_buffers=NBUF, us_median=round(med, 2), us_min=round(best, 2), bytes_per_pixel=per_pixel,
                                      gbps_at_median=round(gbps, 1), gbps_vs_yardstick=round(gbps / yard[pair], 3),
                                      spread_min_vs_median=round(1 - best / med, 3), device=torch.cuda.get_device_name(0))))
-    del frames, cases, p10
+    del frames, frames4, cases, p10
     torch.cuda.empty_cache()
     if args.end_to_end:
         for mode, runs in end_to_end(args.steps).items():

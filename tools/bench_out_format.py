@@ -1,4 +1,4 @@
-"""Same-process timing of the output-format kernels of the Y4M front end (csrc/colorfix.hip K13, `uav_clip_window_to_yuv`) against the
+"""Same-process timing of the output-format kernels of the Y4M front end (csrc/yuv_io.hip K13, `uav_clip_window_to_yuv`) against the
 8-bit 4:2:0 kernel they stand beside, in the style of tools/bench_yuv_io.py.
   frames (8,3,1280,1280) fp32, 12 B read per pixel; written per pixel: uav_clip_to_yuv420_u8 1.5 B (the yardstick), the window
   kernel for 420 1.5 B, 444 3 B, 420p10 3 B, 444p10 6 B.

@@ -1,4 +1,4 @@
-"""Same-process timing of the frame I/O kernels around the pipeline call (csrc/colorfix.hip K13): the Y'CbCr pair of the Y4M
+"""Same-process timing of the frame I/O kernels around the pipeline call (csrc/yuv_io.hip K13): the Y'CbCr pair of the Y4M
 front end against the RGB pair it stands beside.
   out side, frames (8,3,1280,1280):  uav_clip_to_yuv420_u8 (12 B read + 1.5 B written per pixel)  vs  uav_clip_to_frames_u8 (12 + 3)
   in side,  clip   (8,3,320,320):    uav_yuv420_to_clip_f32 (1.5 B read + 12 B written)           vs  uav_frames_to_clip_f32 from uint8 (3 + 12)

@@ -1392,26 +1392,7 @@ def clip_window_to_yuv420_u8(window, y, cb, cr, coefs, frames_first=False):
     """`clip_to_yuv420_u8` without a copy on either side: `window` is any fp32 VIEW (3,T,h,w) — `frames_first`: (T,3,h,w) — with
     unit pixel stride (a crop of the decoder's output, say), `y` (T,h,w) and `cb`, `cr` (T,h/2,w/2) are uint8 views into larger
     planes (unit pixel stride; cb and cr with the same strides), which receive the window's samples; nothing else is written."""
-    lib = _lib.load()
-    if window.dim() != 4 or window.shape[1 if frames_first else 0] != 3:
-        raise _lib.UavError("clip_window_to_yuv420_u8: a (3,T,h,w) view expected, (T,3,h,w) with frames_first")
-    c_dim, t_dim = (1, 0) if frames_first else (0, 1)
-    t, (h, w) = window.shape[t_dim], window.shape[2:]
-    if h % 2 or w % 2:
-        raise _lib.UavError(f"clip_window_to_yuv420_u8: h and w must be even for 4:2:0 planes, got {h}x{w} (UAV_ESHAPE)")
-    for name, p, dtype, shape in (("window", window, torch.float32, tuple(window.shape)), ("y", y, torch.uint8, (t, h, w)),
-                                  ("cb", cb, torch.uint8, (t, h // 2, w // 2)), ("cr", cr, torch.uint8, (t, h // 2, w // 2))):
-        if not p.is_cuda or p.device != window.device or p.dtype != dtype or tuple(p.shape) != shape or p.stride(-1) != 1:
-            raise _lib.UavError(f"clip_window_to_yuv420_u8: {name} must be a {dtype} view of shape {shape} with unit pixel stride on "
-                                f"the window's GPU, got {p.dtype} {tuple(p.shape)} strides {p.stride()} on {p.device}")
-    if cb.stride() != cr.stride():
-        raise _lib.UavError("clip_window_to_yuv420_u8: cb and cr must share their strides")
-    k = _coef_array(coefs.forward, 10, "clip_window_to_yuv420_u8")
-    def pitch(p):                                   # torch leaves the stride of a size-1 dimension arbitrary; no second row is addressed
-        return p.stride(1) if p.shape[1] > 1 else max(p.stride(1), p.shape[2])
-    rc = lib.uav_clip_window_to_yuv420_u8(_p(window), window.stride(c_dim), window.stride(t_dim), window.stride(2), _p(y), pitch(y),
-                                          y.stride(0), _p(cb), _p(cr), pitch(cb), cb.stride(0), t, h, w, k, _stream())
-    _lib.check(rc, "uav_clip_window_to_yuv420_u8")
+    clip_window_to_yuv(window, y, cb, cr, coefs, chroma444=False, depth=8, frames_first=frames_first)
 
 
 def clip_window_to_yuv(window, y, cb, cr, coefs, *, chroma444, depth, frames_first=False):

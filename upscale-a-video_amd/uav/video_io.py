@@ -9,7 +9,7 @@ Two kernel passes mirror what the reference CLI does with chains of eager tensor
 
 and two more take the place of a decoder / encoder's colour conversion for the one container the engine reads and writes
 itself, YUV4MPEG2 (`.y4m`: uncompressed planar Y'CbCr, what `ffmpeg -i in.mp4 in.y4m` / `ffmpeg -i out.y4m out.mp4`
-produce and eat), in 16.16 fixed point so that every byte is defined (csrc/colorfix.hip, K13):
+produce and eat), in 16.16 fixed point so that every byte is defined (csrc/yuv_io.hip, K13):
 
     clip = preprocess_planes(read_y4m(path), device)        # planes -> (1,3,T,h,w), same normalisation and pooling
     y, cb, cr = postprocess_planes(output, coefs)           # (T,3,H,W) in [-1,1] -> 4:2:0 planes; write_y4m(path, y, cb, cr, ...)
