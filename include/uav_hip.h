@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 11
+#define UAV_ABI_VERSION 12
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -627,6 +627,21 @@ int uav_yuv420_sited_to_clip_f32(const void* y, const void* cb, const void* cr, 
  * The largest intermediate is 2^28 for both depths. */
 int uav_clip_to_yuv420_sited(const float* frames_tchw, void* y, void* cb, void* cr, int32_t t_len, int32_t h, int32_t w,
                              int32_t depth, const int32_t* coefs, void* stream);
+
+/* Scene statistics of a clip (the front end's `--scenes auto`; csrc/scene_stats.hip): the contiguous clip (3,T,h,w) fp32 in
+ * [-1,1] — what the network sees — -> hist [T][64] int32 and sad [T] int64, all in integers, every output defined bit for bit.
+ * coefs = {fy[3], fcb[3], fcr[3], yo}, a forward table of depth 8 as uav_clip_to_yuv420_u8 takes it (only fy and yo are used).
+ * Per pixel and frame t:
+ *   q_c = the uint8 RGB value as uav_clip_to_frames_u8 forms it: (int)(clamp(x_c/2 + 0.5, 0, 1) * 255)
+ *   Y   = clamp(((fy[0]*q_r + fy[1]*q_g + fy[2]*q_b + 32768) >> 16) + yo, 0, 255), the luma uav_clip_to_yuv420_u8 writes
+ *   hist[t][Y >> 2] += 1
+ *   sad[t] = sum over the frame of |Y[t] - Y[t-1]| for t >= 1; sad[0] = 0.
+ * Both outputs are zeroed on `stream` before the launch; sad is accumulated in 64 bits (255*h*w passes 2^31 at 4K).  Any
+ * h, w >= 1; 16-byte loads when the clip's base is 16-byte aligned and h*w % 4 == 0, scalar ones otherwise, same result.
+ * A null pointer: UAV_EINVAL; t_len <= 0, t_len > 65535, h <= 0, w <= 0 or 2^31 blocks and more: UAV_ESHAPE — all before any
+ * memset or launch.  A memset or the launch that fails returns its hipError_t, positive, as every failed launch of this ABI does. */
+int uav_clip_scene_stats(const float* clip_cthw, int32_t t_len, int32_t h, int32_t w, int32_t* hist, int64_t* sad,
+                         const int32_t* coefs, void* stream);
 
 #ifdef __cplusplus
 }

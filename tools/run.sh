@@ -27,6 +27,7 @@
 #   yuvio           tools/bench_yuv_io.py: the Y4M front end's Y'CbCr kernels vs the RGB frame conversions, 20 warm launches each (kept copy: profiles/yuv_io_kernels.jsonl)
 #   outfmt          tools/bench_out_format.py: the --out-format kernels (444, 420p10, 444p10) vs uav_clip_to_yuv420_u8 in one process (kept copy: profiles/out_format_kernels.txt)
 #   chroma          tools/bench_chroma_sited.py: the --chroma sited kernels vs the replicate / block-mean kernels beside them in one process, and one tiled job per mode (kept copy: profiles/chroma_sited_kernels.txt)
+#   scenes          tools/bench_scene_stats.py: uav_clip_scene_stats (--scenes auto) vs uav_clip_to_yuv420_u8 on the same bytes in one process, and one cut-free job per mode (kept copy: profiles/scene_stats_kernel.txt)
 #   outsize         tools/bench_out_size.py: uav_resize_aa_f32 (--out-size / --out-scale) vs uav_clip_to_yuv420_u8 in one process, and its worst error (kept copy: profiles/out_size_kernels.txt)
 # Environment: any UAV_* variable is passed through to every step.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -150,6 +151,7 @@ PY
     outfmt)   timeout 300 python $R/tools/bench_out_format.py --out $O/${TAG}_out_format_kernels.txt 2>&1 | grep -v amdgpu.ids ;;
     outsize)  timeout 400 python $R/tools/bench_out_size.py --out $O/${TAG}_out_size_kernels.txt 2>&1 | grep -v amdgpu.ids ;;
     chroma)   timeout 420 python $R/tools/bench_chroma_sited.py --end-to-end --out $O/${TAG}_chroma_sited_kernels.txt 2>&1 | grep -v amdgpu.ids ;;
+    scenes)   timeout 420 python $R/tools/bench_scene_stats.py --end-to-end --out $O/${TAG}_scene_stats_kernel.txt 2>&1 | grep -v amdgpu.ids ;;
     *)        echo "unknown step $step" ;;
   esac
 done

@@ -8,6 +8,7 @@
 //                                                      uav_clip_to_yuv420_sited
 #include <type_traits>
 #include "uav_common.h"
+#include "yuv_common.h"
 #include "yuv_mode.h"
 
 namespace {
@@ -69,8 +70,7 @@ extern "C" int uav_clip_to_frames_u8(const float* frames_tchw, void* frames_thwc
 // The launchers pick the mode from W and the alignment of every address a thread forms (yuv_mode.h).  No LDS, no scratch.
 namespace {
 constexpr int YUV_RUN = 8;
-struct YuvInv { int yo, iy, rcr, gcb, gcr, bcb; };
-struct YuvFwd { int fy[3], fcb[3], fcr[3], yo; };
+struct YuvInv { int yo, iy, rcr, gcb, gcr, bcb; };                             // YuvFwd: yuv_common.h
 
 // What a thread owns: pixels [x0, x0 + n) of the rows [y0, y0 + rows) of frame t; ry = y0 / 2 is its chroma row in 4:2:0.
 struct YuvOwn { int t, ry, x0, y0, rows, n; };
@@ -86,12 +86,7 @@ UAV_DEVINL bool yuv_own(int h, int w, YuvOwn& o) {
 UAV_DEVINL int yuv_clamp255(int v) { return min(max(v, 0), 255); }
 // uint8 value -> [-1,1], the expression of frames_to_clip_kernel
 UAV_DEVINL float yuv_u8_to_clip(int v) { return ((float)v / 255.0f - 0.5f) * 2.0f; }
-// [-1,1] -> uint8 value, the expression of clip_to_u8_kernel
-UAV_DEVINL int yuv_clip_to_u8(float x) {
-    float v = x / 2.0f + 0.5f;
-    v = fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f;
-    return (int)v;
-}
+// ([-1,1] -> uint8 value, the expression of clip_to_u8_kernel: yuv_clip_to_u8 in yuv_common.h)
 UAV_DEVINL void yuv_to_rgb(const YuvInv& k, int yy, int u, int v, float& r, float& g, float& b) {
     const int y = (yy - k.yo) * k.iy;
     u -= 128; v -= 128;
@@ -272,9 +267,7 @@ __global__ __launch_bounds__(256) void yuv_sited_to_clip_kernel(const unsigned c
 // per 2x2 block (the four products summed before the one rounding).  SITED (4:2:0 only): horizontally co-sited and vertically
 // centred chroma, the siting of `C420mpeg2` and `C420p10` — a sample is made from the (1,2,1) filter around its EVEN luma
 // column in both rows of its block, weights totalling 8, one rounding; a thread reads one more column, x0 - 1 (clamped to the
-// window), per row and channel.
-template <bool D10> struct YuvDepth { typedef unsigned char sample; static constexpr int centre = 128, vmax = 255; };
-template <> struct YuvDepth<true> { typedef unsigned short sample; static constexpr int centre = 512, vmax = 1023; };
+// window), per row and channel.  YuvDepth, yuv_clampd and yuv_luma_d are shared with the scene statistics: yuv_common.h.
 
 // [-1,1] -> 12-bit value: the clamp of clip_to_u8_kernel, rounded to 0..4095
 UAV_DEVINL int yuv_clip_to_q12(float x) {
@@ -284,10 +277,6 @@ UAV_DEVINL int yuv_clip_to_q12(float x) {
     return (int)(v * 4095.0f + 0.5f);
 }
 template <bool D10> UAV_DEVINL int yuv_quant(float x) { return D10 ? yuv_clip_to_q12(x) : yuv_clip_to_u8(x); }
-template <bool D10> UAV_DEVINL int yuv_clampd(int v) { return min(max(v, 0), YuvDepth<D10>::vmax); }
-template <bool D10> UAV_DEVINL int yuv_luma_d(const YuvFwd& k, int r, int g, int b) {
-    return yuv_clampd<D10>(((k.fy[0] * r + k.fy[1] * g + k.fy[2] * b + 32768) >> 16) + k.yo);
-}
 // a chroma sample from R, G, B weights totalling 2^(SHIFT - 16): of one pixel (yuv_chroma1), of the sums of a 2x2 block
 // (yuv_chroma4), of the sited filter's sums (yuv_chroma8)
 template <bool D10, int SHIFT> UAV_DEVINL int yuv_chroma_n(const int* f, int r, int g, int b) {
@@ -428,7 +417,6 @@ __global__ __launch_bounds__(256) void clip_to_yuv_kernel(const float* __restric
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 inline YuvInv yuv_inv(const int32_t* c) { return {c[0], c[1], c[2], c[3], c[4], c[5]}; }
-inline YuvFwd yuv_fwd(const int32_t* c) { return {{c[0], c[1], c[2]}, {c[3], c[4], c[5]}, {c[6], c[7], c[8]}, c[9]}; }
 inline uintptr_t yuv_addr(const void* p) { return (uintptr_t)p; }
 
 // one thread per YUV_RUN x 2 pixels of a frame, the frames along y; false: more blocks than a grid dimension holds

@@ -8,23 +8,31 @@ or, with no file in between (`-i -` reads one Y4M stream from standard input, `-
 
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python upscale.py -i - --y4m-out - --pretrained DIR | ffmpeg -i - out.mp4
 
-(`python -m uav.cli` with `upscale-a-video_amd` on the path is the same program.)  It takes the options of the reference
+(`python -m uav.cli` with `upscale-a-video_amd` on the path is the same program.) It takes the options of the reference
 project's `inference_upscale_a_video.py` and does per video what that program does — `video_io.upscale_clip_chunks` — 3 output
-frames at a time: the input is read whole (the DDIM loop needs all of it, at 1/16 of the output's size), the 4x frames go to
-the file chunk by chunk and never exist as one clip.  It reads and writes by itself: YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and
-directories of images in; `.y4m` out — `--out-format 420` (8-bit 4:2:0, the default), `444`, `420p10` or `444p10`; the 10-bit
-formats are made from the fp32 frames with no 8-bit step in between and ffmpeg reads all four through the same pipe —, the
-colour conversion on the GPU on both sides (`uav_yuv420_to_clip_f32`, `uav_clip_to_yuv420_u8`, `uav_clip_window_to_yuv`).
-Input stays 8-bit.  `--out-size WxH` (or `W:H`) or `--out-scale S` (1 to 4) write another size than 4x, from the network's input
-size up to 4x of it: 480p material at 1080p is `--out-scale 2.25`.  Each chunk's fp32 frames are resized on the GPU with an
-antialiased cubic filter (`uav_resize_aa_f32`: the filter of `F.interpolate(mode='bicubic', antialias=True)`, after the colour
-fix and before the colour conversion), so only frames of the delivery size reach the host; `--matrix auto` goes by the rows
-written.  `--chroma sited` filters 4:2:0 chroma at the position the tags declare instead of replicating samples on the way in and
-writing block means on the way out: bilinear up-sampling at the input tag's siting (`uav_yuv420_sited_to_clip_f32`) and, for the
-left-sited tags written (`C420mpeg2`, `C420p10`), a (1,2,1) filter around the even column (`uav_clip_to_yuv420_sited`); the default,
-`replicate`, keeps every file's bytes as they were.  `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
-each.  Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the
-caption text, default none.
+frames at a time: the input is read whole unless `--scenes auto` is given (the DDIM loop needs all of a clip, at 1/16 of the
+output's size), the 4x frames go to the file chunk by chunk and never exist as one clip. It reads and writes by itself:
+YUV4MPEG2 (`.y4m`, 8-bit 4:2:0 / 4:4:4, progressive), `.npy` arrays of (T,H,W,3) uint8 RGB and directories of images in; `.y4m`
+out — `--out-format 420` (8-bit 4:2:0, the default), `444`, `420p10` or `444p10`; the 10-bit formats are made from the fp32
+frames with no 8-bit step in between and ffmpeg reads all four through the same pipe —, the colour conversion on the GPU on both
+sides (`uav_yuv420_to_clip_f32`, `uav_clip_to_yuv420_u8`, `uav_clip_window_to_yuv`). Input stays 8-bit. `--out-size WxH` (or
+`W:H`) or `--out-scale S` (1 to 4) write another size than 4x, from the network's input size up to 4x of it: 480p material at
+1080p is `--out-scale 2.25`. Each chunk's fp32 frames are resized on the GPU with an antialiased cubic filter
+(`uav_resize_aa_f32`: the filter of `F.interpolate(mode='bicubic', antialias=True)`, after the colour fix and before the colour
+conversion), so only frames of the delivery size reach the host; `--matrix auto` goes by the rows written. `--chroma sited`
+filters 4:2:0 chroma at the position the tags declare instead of replicating samples on the way in and writing block means on
+the way out: bilinear up-sampling at the input tag's siting (`uav_yuv420_sited_to_clip_f32`) and, for the left-sited tags
+written (`C420mpeg2`, `C420p10`), a (1,2,1) filter around the even column (`uav_clip_to_yuv420_sited`); the default,
+`replicate`, keeps every file's bytes as they were. `--scenes auto` splits a video at its cuts: `uav_clip_scene_stats` makes per
+frame a luma histogram and the absolute difference to the frame before on the GPU, `video_io.scene_cuts` decides on the host
+(`--scene-threshold MAD:HIST`, `--scene-min N`, `--scene-max N`; the defaults are conventional starting values, NOT validated on
+real footage), and every scene goes through `video_io.upscale_clip_chunks` as a clip of its own, one after the other into the
+one output file, so that no temporal window, attention or flow crosses a cut; a `.y4m` input, file or pipe, is then read 48
+frames at a time and only as far as the scene at hand needs (`video_io.Y4MReader`), which bounds the memory by the longest scene
+or `--scene-max` instead of the video. Without it (`--scenes off`, the default) the input is read whole and the video is one
+clip, byte for byte as before. `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
+each. Not there: compressed containers and codecs (use ffmpeg as above) and the LLaVA captioner — `--prompt` takes the caption
+text, default none.
 
 `--pretrained DIR` is the released checkpoint layout: vae/{vae_3d,vae_video}{_config.json,.bin},
 unet/unet_video{_config.json,.bin}, scheduler/, low_res_scheduler/, text_encoder/, tokenizer/ and, for `-p`,
@@ -37,6 +45,9 @@ import time
 from fractions import Fraction
 
 import torch
+
+
+PIECE_FRAMES = 48           # `--scenes auto` reads and analyses the input this many frames at a time
 
 
 class UserError(Exception):
@@ -89,6 +100,18 @@ def build_parser():
     p.add_argument("--chroma", default="replicate", choices=["replicate", "sited"],
                    help="4:2:0 chroma: replicate = samples replicated on input, block means on output (default, the files' bytes as "
                         "ever); sited = filtered at the position the Y4M tags declare, on both sides")
+    p.add_argument("--scenes", default="off", choices=["off", "auto"],
+                   help="auto = find the cuts on the GPU, run every scene as a clip of its own (nothing temporal crosses a cut) and "
+                        "read the input only as far as the scene at hand needs; off (default) = the whole video is one clip")
+    p.add_argument("--scene-threshold", dest="scene_threshold", metavar="MAD:HIST", default="24:0.30",
+                   help="with --scenes auto: a cut needs a mean absolute luma difference >= MAD (8-bit steps) AND a 64-bin histogram "
+                        "distance >= HIST (0 to 1) to the frame before; the defaults are conventional starting values and have NOT "
+                        "been validated on real footage")
+    p.add_argument("--scene-min", dest="scene_min", metavar="N", default="8",
+                   help="with --scenes auto: no scene shorter than N frames (default 8, the network's temporal window); the three "
+                        "--scene-* values are checked whether or not --scenes auto is given")
+    p.add_argument("--scene-max", dest="scene_max", metavar="N", default="0",
+                   help="with --scenes auto: split a scene after N frames even without a cut, which bounds the memory; 0 (default) = never")
     p.add_argument("--seed", type=int, default=10)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
@@ -117,10 +140,70 @@ def _out_size_options(args):
     return size, scale
 
 
+def _scene_options(args):
+    """`--scene-threshold` / `--scene-min` / `--scene-max` as `video_io.upscale_scenes_chunks` takes them: ((MAD, HIST), min, max)."""
+    import math
+    parts = args.scene_threshold.split(":")
+    try:
+        mad, dist = (float(v) for v in parts) if len(parts) == 2 else (math.nan, math.nan)
+    except ValueError:
+        mad = dist = math.nan
+    if not (math.isfinite(mad) and mad >= 0.0 and 0.0 <= dist <= 1.0):
+        raise UserError(f"--scene-threshold: MAD:HIST with MAD >= 0 and HIST from 0 to 1 expected (e.g. 24:0.30), got {args.scene_threshold!r}")
+    counts = []
+    for option, text in (("--scene-min", args.scene_min), ("--scene-max", args.scene_max)):
+        if not (text.isascii() and text.isdigit()):
+            raise UserError(f"{option}: a number of frames expected, got {text!r}")
+        counts.append(int(text))
+    if counts[0] < 1:
+        raise UserError(f"--scene-min: at least 1 frame expected, got {args.scene_min!r}")
+    if 0 < counts[1] < counts[0]:
+        raise UserError(f"--scene-max: 0 (never force a split) or at least --scene-min = {counts[0]} expected, got {args.scene_max!r}")
+    return (mad, dist), counts[0], counts[1]
+
+
+class _Pieces:
+    """One video of `--scenes auto`, read as far as it has been asked for: `size` (H, W) of the input, `fps`, `full_range`, and
+    `clips(device, matrix, chroma)`, the (1,3,n,h,w) clips of `PIECE_FRAMES` frames each.  A `.y4m` input (file or standard input)
+    is a `Y4MReader` whose header and first piece are read here, up front; `.npy` arrays and image directories are read whole,
+    as ever, and sliced."""
+
+    def __init__(self, path):
+        from . import video_io
+        self._reader = self._frames = None
+        try:
+            if path == "-" or (os.path.isfile(path) and str(path).lower().endswith(".y4m")):
+                self._reader = video_io.Y4MReader(sys.stdin.buffer if path == "-" else path)
+                self._first = self._reader.read(PIECE_FRAMES)
+                self.size, self.fps, self.full_range = self._reader.size, self._reader.fps, self._reader.full_range
+            else:
+                self._frames, self.fps = video_io.read_frames(path)
+                self.size, self.full_range = tuple(int(v) for v in self._frames.shape[1:3]), True
+        except (ValueError, OSError) as e:
+            raise UserError(str(e)) from None
+
+    def clips(self, device, matrix, chroma):
+        from . import video_io
+        if self._reader is None:
+            for i in range(0, len(self._frames), PIECE_FRAMES):
+                frames = torch.from_numpy(self._frames[i:i + PIECE_FRAMES]).permute(0, 3, 1, 2).contiguous()
+                yield video_io.preprocess_frames(frames.to(device))
+            return
+        try:
+            piece, self._first = self._first, None
+            while piece is not None:
+                yield video_io.preprocess_planes(piece, device, matrix, chroma=chroma)
+                piece = self._reader.read(PIECE_FRAMES)
+        except (ValueError, OSError) as e:
+            raise UserError(str(e)) from None
+        finally:
+            self._reader.close()
+
+
 def _output_size(source, size, scale, fmt):
     """(H, W) to write for one video read by `_read`; a size outside the video's range is a UserError."""
     from . import video_io
-    in_h, in_w = source.size if isinstance(source, video_io.Y4MClip) else source.shape[1:3]
+    in_h, in_w = source.size if isinstance(source, (video_io.Y4MClip, _Pieces)) else source.shape[1:3]
     h, w = video_io.pooled_size(int(in_h), int(in_w))
     try:
         return video_io.output_size(4 * h, 4 * w, out_size=size, out_scale=scale, fmt=fmt)
@@ -210,13 +293,15 @@ def _read(path):
 def run(args):
     from . import tiling, video_io
     size, scale = _out_size_options(args)
+    scene = _scene_options(args)
+    auto = args.scenes == "auto"
     videos = ["-"] if args.input_path == "-" else list_videos(args.input_path)
     if args.y4m_out is not None and len(videos) > 1:
         raise UserError(f"--y4m-out takes one video, {args.input_path} holds {len(videos)}")
     device = torch.device(args.device)
     if device.type == "cuda" and not torch.cuda.is_available():
         raise UserError(f"--device {args.device}: no GPU is visible")
-    first = _read(videos[0])                # before the checkpoints are loaded: an unreadable input fails at once
+    first = (_Pieces(videos[0]), None) if auto else _read(videos[0])                # before the checkpoints are loaded: an unreadable input fails at once
     fmt = video_io.out_format(args.out_format)
     _output_size(first[0], size, scale, fmt)                # ... and so does a size the first video cannot have
     pipeline, raft = load_pipeline(args.pretrained, use_video_vae=args.use_video_vae, with_propagator=bool(args.propagation_steps),
@@ -224,21 +309,23 @@ def run(args):
     prompt = args.prompt + args.a_prompt
     out_path = None
     for index, path in enumerate(videos):
-        source, fps = first if index == 0 else _read(path)
+        source, fps = first if index == 0 else ((_Pieces(path), None) if auto else _read(path))
         first = None
         out_h, out_w = _output_size(source, size, scale, fmt)
         name = "stdin" if path == "-" else os.path.splitext(os.path.basename(os.path.normpath(path)))[0]
-        if isinstance(source, video_io.Y4MClip):
+        if auto:
+            clip, fps, in_size = None, source.fps, source.size
+        elif isinstance(source, video_io.Y4MClip):
             clip = video_io.preprocess_planes(source, device, args.matrix, chroma=args.chroma)
             in_size = source.size
         else:
             frames = torch.from_numpy(source).permute(0, 3, 1, 2).contiguous()
             clip = video_io.preprocess_frames(frames.to(device))
             in_size = tuple(source.shape[1:3])
-        t, (h, w) = clip.shape[2], clip.shape[-2:]
+        t, (h, w) = (None, video_io.pooled_size(*in_size)) if auto else (clip.shape[2], clip.shape[-2:])
         tiles = len(tiling.tile_grid(h, w, args.tile_size)) if tiling.needs_tiling(h, w, args.perform_tile) else 1
         generator = torch.Generator(device=device).manual_seed(args.seed)
-        full_range = source.full_range if isinstance(source, video_io.Y4MClip) else True
+        full_range = source.full_range if isinstance(source, (video_io.Y4MClip, _Pieces)) else True
         coefs = video_io.yuv_coefficients(video_io.auto_matrix(out_h) if args.matrix == "auto" else args.matrix, full_range,
                                           depth=fmt.depth)
         prop = "_p" + "_".join(map(str, args.propagation_steps)) if args.propagation_steps else ""
@@ -254,12 +341,15 @@ def run(args):
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         start = time.time()
-        chunks = video_io.upscale_clip_chunks(pipeline, clip, prompt=prompt, negative_prompt=args.n_prompt, raft=raft,
-                                              propagation_steps=args.propagation_steps, steps=args.inference_steps,
-                                              guidance_scale=args.guidance_scale, noise_level=args.noise_level, tile_size=args.tile_size,
-                                              perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
-                                              coefs=None if need_frames else coefs, fmt=fmt,
-                                              out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w), chroma=args.chroma)
+        options = dict(prompt=prompt, negative_prompt=args.n_prompt, raft=raft, propagation_steps=args.propagation_steps,
+                       steps=args.inference_steps, guidance_scale=args.guidance_scale, noise_level=args.noise_level,
+                       tile_size=args.tile_size, perform_tile=args.perform_tile, color_fix=args.color_fix, generator=generator,
+                       coefs=None if need_frames else coefs, fmt=fmt,
+                       out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w), chroma=args.chroma)
+        if auto:        # scene by scene, the input read piece by piece as the scenes need it
+            chunks = video_io.upscale_scenes_chunks(pipeline, source.clips(device, args.matrix, args.chroma), scene=scene, **options)
+        else:
+            chunks = video_io.upscale_clip_chunks(pipeline, clip, **options)
         with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, out_w, out_h, args.fps or fps or 24, full_range,
                                 fmt) as out:
             for chunk in chunks:                                # one chunk is alive: decoded, converted and written before the next
@@ -279,7 +369,13 @@ def run(args):
             import numpy as np
             with open(args.dump_rgb, "wb") as fh:
                 np.save(fh, np.concatenate(dump))
-        print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {out_h}x{out_w}, {tiles} tile(s), "
+        scenes = ""
+        if auto:
+            t, starts = chunks.frames, [a for a, _ in chunks.scenes[1:]]
+            scenes = f", {len(chunks.scenes)} scene(s)"
+            if starts:
+                scenes += " (cuts at " + ", ".join(map(str, starts[:12])) + (", …" if len(starts) > 12 else "") + ")"
+        print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {out_h}x{out_w}, {tiles} tile(s){scenes}, "
               f"{seconds:.2f} s -> {out_path}", file=sys.stderr if out_path == "-" else sys.stdout, flush=True)
     return out_path
 

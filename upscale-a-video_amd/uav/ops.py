@@ -1476,3 +1476,21 @@ def clip_to_yuv420_sited(frames, coefs, depth=8):
     cr = torch.empty_like(cb)
     _lib.check(lib.uav_clip_to_yuv420_sited(_p(frames), _p(y), _p(cb), _p(cr), t, h, w, depth, k, _stream()), "uav_clip_to_yuv420_sited")
     return y, cb, cr
+
+
+def clip_scene_stats(clip, coefs):
+    """The contiguous clip (3,T,h,w) fp32 in [-1,1] -> (hist int32 (T,64), sad int64 (T,)) on the clip's device: per frame the
+    64-bin histogram of the 8-bit luma `clip_to_yuv420_u8` would write with `coefs` (a forward table of depth 8) and the sum of
+    absolute luma differences to the frame before (sad[0] = 0), all in integers (`uav_clip_scene_stats`, one pass over the clip)."""
+    lib = _lib.load()
+    _req(clip, torch.float32, "clip")
+    if clip.dim() != 4 or clip.shape[0] != 3:
+        raise _lib.UavError(f"clip_scene_stats: a (3,T,h,w) fp32 clip expected, got {tuple(clip.shape)}")
+    if getattr(coefs, "depth", 8) != 8:
+        raise _lib.UavError("clip_scene_stats: the forward table of depth 8 expected")
+    _, t, h, w = clip.shape
+    k = _coef_array(coefs.forward, 10, "clip_scene_stats")
+    hist = torch.empty((t, 64), dtype=torch.int32, device=clip.device)
+    sad = torch.empty((t,), dtype=torch.int64, device=clip.device)
+    _lib.check(lib.uav_clip_scene_stats(_p(clip), t, h, w, _p(hist), _p(sad), k, _stream()), "uav_clip_scene_stats")
+    return hist, sad

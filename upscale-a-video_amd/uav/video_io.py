@@ -28,6 +28,14 @@ default.  `chroma="sited"` (`--chroma sited`) filters at the position the tags d
 on the way in (`uav_yuv420_sited_to_clip_f32`) and, for the left-sited tags written (`C420mpeg2`, `C420p10`), the (1,2,1) filter
 around the even column on the way out (`uav_clip_to_yuv420_sited`).
 
+Scenes (`--scenes auto`): `upscale_scenes_chunks` takes a video as an iterator of pieces — `Y4MReader` reads a `.y4m` file or
+pipe that way, with `read_y4m`'s header parser and refusals —, gets each piece's integer statistics from `ops.clip_scene_stats`
+(per frame a 64-bin luma histogram and the sum of absolute luma differences to the frame before, csrc/scene_stats.hip), lets
+`SceneCutter`, the streaming form of the pure function `scene_cuts`, find the cuts, and runs `upscale_clip_chunks` on every
+scene as a clip of its own with one shared generator; nothing temporal crosses a cut and no more input is held than the open
+scene needs. The detector's defaults (`SCENE_THRESHOLD`, `SCENE_MIN_LEN`) are conventional starting values that have not been
+validated on real footage. Without it a video is one clip and is read whole.
+
 Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
 import os
@@ -248,19 +256,9 @@ def _new_planes(like, t, h, w, fmt: OutFormat):
 
 # ------------------------------------------------------------------------------------------------
 # YUV4MPEG2
-def read_y4m(path) -> Y4MClip:
-    """Read a progressive 8-bit YUV4MPEG2 file — `path`, or an open binary stream such as a pipe, named by its `.name` in
-    messages — whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
-    (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is not applied here: the tag is kept in `colorspace`, and
-    `preprocess_planes` replicates a sample over its 2x2 block by default or, with `chroma="sited"`, filters at `chroma_siting(tag)`.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
-    rest.  Anything else (4:2:2, mono, more than 8 bits, interlaced, a truncated frame) raises ValueError naming the tag."""
-    import numpy as np
-    if hasattr(path, "read"):
-        data, path = path.read(), getattr(path, "name", "<stream>")
-    else:
-        with open(path, "rb") as fh:
-            data = fh.read()
-    end = data.find(b"\n")
+def _parse_y4m_header(data: bytes, end: int, path):
+    """The stream header of a YUV4MPEG2 file — `data` from its first byte, `end` the index of the first newline (-1: none) — as
+    (w, h, fps, colorspace, full_range); every refusal of `read_y4m` and `Y4MReader` about the header is raised here."""
     if not data.startswith(b"YUV4MPEG2") or end < 0 or (end > 9 and data[9:10] != b" "):
         raise ValueError(f"{path}: not a YUV4MPEG2 file (no 'YUV4MPEG2' signature line)")
     w = h = None
@@ -291,6 +289,23 @@ def read_y4m(path) -> Y4MClip:
         raise ValueError(f"{path}: the header has no valid W / H tags")
     if full_range is None:
         full_range = colorspace == "C420jpeg"
+    return w, h, fps, colorspace, full_range
+
+
+def read_y4m(path) -> Y4MClip:
+    """Read a progressive 8-bit YUV4MPEG2 file — `path`, or an open binary stream such as a pipe, named by its `.name` in
+    messages — whole.  Chroma `C420jpeg`, `C420mpeg2`, `C420paldv`, `C420` or no `C` tag
+    (= 4:2:0, as the format defines) and `C444`.  Chroma SITING is not applied here: the tag is kept in `colorspace`, and
+    `preprocess_planes` replicates a sample over its 2x2 block by default or, with `chroma="sited"`, filters at `chroma_siting(tag)`.  Range: `XCOLORRANGE=FULL|LIMITED` when present, else full for `C420jpeg` and limited for the
+    rest.  Anything else (4:2:2, mono, more than 8 bits, interlaced, a truncated frame) raises ValueError naming the tag."""
+    import numpy as np
+    if hasattr(path, "read"):
+        data, path = path.read(), getattr(path, "name", "<stream>")
+    else:
+        with open(path, "rb") as fh:
+            data = fh.read()
+    end = data.find(b"\n")
+    w, h, fps, colorspace, full_range = _parse_y4m_header(data, end, path)
     ch, cw = (h, w) if colorspace == "C444" else ((h + 1) // 2, (w + 1) // 2)
     ysz, csz = h * w, ch * cw
     pos, offsets = end + 1, []
@@ -310,6 +325,81 @@ def read_y4m(path) -> Y4MClip:
     cb = np.stack([buf[o + ysz:o + ysz + csz].reshape(ch, cw) for o in offsets])
     cr = np.stack([buf[o + ysz + csz:o + ysz + 2 * csz].reshape(ch, cw) for o in offsets])
     return Y4MClip(y, cb, cr, fps, (h, w), colorspace, full_range)
+
+
+class Y4MReader:
+    """`read_y4m` in pieces: the header is parsed on construction by the same code (every refusal and message is `read_y4m`'s),
+    then `read(n)` returns the next up to `n` frames as a `Y4MClip`, or None at the end of the input.  `path_or_stream`: a path,
+    or an open binary stream such as a pipe — nothing seeks and nothing is read past the frames asked for (Python's own
+    buffering aside).  `fps`, `size` = (H, W), `colorspace` and `full_range` are the header's; `frames_read` counts the frames
+    returned so far.  A frame cut short and a missing 'FRAME' raise `read_y4m`'s ValueError with the same frame index / byte offset."""
+    _LINE = 1 << 16                                    # longest header / FRAME line looked at
+
+    def __init__(self, path_or_stream):
+        self._own = not hasattr(path_or_stream, "read")
+        self.name = os.fspath(path_or_stream) if self._own else getattr(path_or_stream, "name", "<stream>")
+        self._fh = open(path_or_stream, "rb") if self._own else path_or_stream
+        try:
+            line = self._fh.readline(self._LINE)
+            w, h, self.fps, self.colorspace, self.full_range = _parse_y4m_header(line, line.find(b"\n"), self.name)
+        except BaseException:
+            self.close()
+            raise
+        self.size, self.frames_read, self._pos = (h, w), 0, len(line)
+        ch, cw = (h, w) if self.colorspace == "C444" else ((h + 1) // 2, (w + 1) // 2)
+        self._cshape, self._ysz, self._csz = (ch, cw), h * w, ch * cw
+
+    def _read_exact(self, n):
+        parts, got = [], 0
+        while got < n:
+            part = self._fh.read(n - got)
+            if not part:
+                break
+            parts.append(part)
+            got += len(part)
+        return parts[0] if len(parts) == 1 else b"".join(parts)
+
+    def read(self, n: int):
+        import numpy as np
+        if n < 1:
+            raise ValueError(f"Y4MReader.read: a positive number of frames expected, got {n}")
+        size, frames = self._ysz + 2 * self._csz, []
+        while len(frames) < n and self._fh is not None:
+            line = self._fh.readline(self._LINE)
+            if not line:
+                break
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise ValueError(f"{self.name}: 'FRAME' expected at byte {self._pos}")
+            self._pos += len(line)                                         # parameters on the FRAME line are skipped
+            data = self._read_exact(size)
+            if len(data) < size:
+                raise ValueError(f"{self.name}: frame {self.frames_read + len(frames)} is truncated ('FRAME' with {len(data)} of "
+                                 f"{size} bytes)")
+            self._pos += size
+            frames.append(data)
+        if not frames:
+            if self.frames_read == 0:
+                raise ValueError(f"{self.name}: no 'FRAME' in the file")
+            return None
+        self.frames_read += len(frames)
+        buf = np.frombuffer(b"".join(frames), dtype=np.uint8).reshape(len(frames), size)
+        (h, w), (ch, cw), ysz, csz = self.size, self._cshape, self._ysz, self._csz
+        y = buf[:, :ysz].reshape(-1, h, w).copy()
+        cb = buf[:, ysz:ysz + csz].reshape(-1, ch, cw).copy()
+        cr = buf[:, ysz + csz:].reshape(-1, ch, cw).copy()
+        return Y4MClip(y, cb, cr, self.fps, self.size, self.colorspace, self.full_range)
+
+    def close(self) -> None:
+        fh, self._fh = getattr(self, "_fh", None), None
+        if fh is not None and self._own:
+            fh.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def y4m_header(w: int, h: int, fps, full_range: bool, fmt="420") -> bytes:
@@ -528,3 +618,170 @@ def upscale_clip(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=
         pipeline, clip, prompt=prompt, negative_prompt=negative_prompt, raft=raft, propagation_steps=propagation_steps, steps=steps,
         guidance_scale=guidance_scale, noise_level=noise_level, tile_size=tile_size, perform_tile=perform_tile, color_fix=color_fix,
         generator=generator, out_size=out_size)))
+
+
+# ------------------------------------------------------------------------------------------------
+# scenes: cuts from the integer statistics of `ops.clip_scene_stats`, one clip per scene
+SCENE_THRESHOLD = (24.0, 0.30)          # (MAD in 8-bit luma steps, histogram distance in [0, 1]): conventional starting values of
+#                                         content detectors, NOT validated on real footage
+SCENE_MIN_LEN = 8                       # the temporal window of the network: a shorter scene stays with its neighbour
+SCENE_BINS = 64
+
+
+class SceneCutter:
+    """The decision of `scene_cuts`, fed piece by piece: `push(sad, hist)` takes the statistics of the next frames (sad[i] against
+    the frame before, whichever piece that was in; the very first frame's is ignored) and returns the cuts that are certain by
+    now, as absolute frame indices; `finish()` returns those the end of the input decides.  All cuts, in order, are in `.cuts`:
+    the same list as one `scene_cuts(..., final=True)` call on the whole arrays, however the input was cut into pieces."""
+
+    def __init__(self, pixels: int, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MIN_LEN, max_len=0):
+        self.mad_min, self.hist_min = (float(v) for v in threshold)
+        self.pixels, self.min_len, self.max_len = int(pixels), int(min_len), int(max_len)
+        if self.pixels < 1 or self.min_len < 1 or self.mad_min < 0 or not 0.0 <= self.hist_min <= 1.0:
+            raise ValueError(f"scene detection needs pixels >= 1, min_len >= 1, MAD >= 0 and a histogram distance in [0, 1], got "
+                             f"{pixels!r}, {min_len!r}, {threshold!r}")
+        if self.max_len < 0 or 0 < self.max_len < self.min_len:
+            raise ValueError(f"max_len must be 0 (never force a split) or at least min_len = {self.min_len}, got {max_len!r}")
+        self.frames, self.cuts = 0, []
+        self._start, self._pending, self._last_hist = 0, [], None
+
+    def push(self, sad, hist):
+        import numpy as np
+        sad, hist = np.asarray(sad, dtype=np.int64).reshape(-1), np.asarray(hist, dtype=np.int64)
+        if hist.shape != (len(sad), SCENE_BINS):
+            raise ValueError(f"scene statistics: sad (n,) and hist (n, {SCENE_BINS}) expected, got {sad.shape} and {hist.shape}")
+        if len(sad) == 0:
+            return []
+        before = hist[:1] if self._last_hist is None else self._last_hist[None]
+        mad = sad.astype(np.float64) / self.pixels
+        hd = np.abs(np.diff(np.concatenate([before, hist]), axis=0)).sum(axis=1).astype(np.float64) / (2.0 * self.pixels)
+        hit = (mad >= self.mad_min) & (hd >= self.hist_min)
+        if self.frames == 0:
+            hit[0] = False                              # no frame before the first
+        self._pending.extend(int(i) + self.frames for i in np.nonzero(hit)[0])
+        self._last_hist, self.frames = hist[-1].copy(), self.frames + len(sad)
+        return self._scan()
+
+    def finish(self):
+        """The end of the input: a cut needs min_len known frames after it whether more may follow or not, so what the last
+        `push` left open stays one scene and nothing is added."""
+        return self._scan()
+
+    def _scan(self):
+        new = []
+        while True:
+            # a candidate nearer than min_len to the scene's start stays inside the scene
+            self._pending = [t for t in self._pending if t - self._start >= self.min_len]
+            events = self._pending[:1] + ([self._start + self.max_len] if self.max_len > 0 else [])
+            t = min(events, default=self.frames)
+            if t >= self.frames or self.frames - t < self.min_len:
+                # not seen yet, or too near the end of what is known: more frames decide — and when none come, this one and
+                # every later one is too near the end
+                break
+            new.append(t)
+            self._start = t
+        self.cuts.extend(new)
+        return new
+
+
+def scene_cuts(sad, hist, pixels, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MIN_LEN, max_len=0, final=True):
+    """The first frames of the scenes 2, 3, ... of a clip of T frames, from `ops.clip_scene_stats`' integers `sad` (T,) and `hist`
+    (T,64) and `pixels` = h*w.  For t >= 1, in float64: mad[t] = sad[t] / pixels (8-bit luma steps) and hd[t] = sum_b |hist[t][b] -
+    hist[t-1][b]| / (2 pixels) in [0, 1]; frame t is a candidate iff mad[t] >= M AND hd[t] >= D, `threshold` = (M, D) — fast motion
+    moves the MAD but not the histogram, a fade the histogram but hardly the MAD of neighbouring frames.  Candidates are taken in
+    ascending order, s the current scene's start: t is a cut iff t - s >= min_len and T - t >= min_len, so flashes and stubs stay
+    with a neighbour.  `max_len` = N > 0 forces a split at s + N when no cut fell in (s, s + N], under the same rule for the tail.
+    `final=False`: T is what has been seen so far and more may follow — only the cuts that min_len known further frames make
+    certain are returned, which is the same rule for the tail: both forms give one list for the same arrays, and a longer
+    input only appends to it (`SceneCutter` is this form with a memory).  The defaults are conventional starting values and have NOT
+    been validated on real footage."""
+    cutter = SceneCutter(pixels, threshold=threshold, min_len=min_len, max_len=max_len)
+    cutter.push(sad, hist)
+    if final:
+        cutter.finish()
+    return list(cutter.cuts)
+
+
+class SceneChunks:
+    """The iterator `upscale_scenes_chunks` returns: the chunks of scene after scene; `.scenes` is the list of (start, end) frame
+    ranges of the scenes begun so far and `.frames` the number of input frames pulled."""
+
+    def __init__(self, pipeline, pieces, scene, kwargs):
+        threshold, min_len, max_len = scene
+        self.scenes, self.frames = [], 0
+        self._scene = dict(threshold=threshold, min_len=min_len, max_len=max_len)
+        SceneCutter(1, **self._scene)                                       # bad options raise here, not at the first chunk
+        self._gen = self._run(pipeline, iter(pieces), kwargs)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._gen)
+
+    def close(self):
+        self._gen.close()
+
+    def _run(self, pipeline, pieces, kwargs):
+        coefs = yuv_coefficients("bt601", True)         # the detector's luma: one table for every input, like its thresholds
+        held, base, last, cutter = [], 0, None, None    # frames [base, self.frames) wait in `held`; `last`: the newest frame
+
+        def scene_clip(end):
+            """Take the frames [base, end) out of `held` as one contiguous clip.  The pieces are copied into it one by one and
+            let go as they are, so the scene and one piece exist at a time, not the scene twice."""
+            nonlocal base
+            n = end - base
+            self.scenes.append((base, end))
+            base = end
+            if len(held) == 1 and held[0].shape[2] == n and held[0].is_contiguous():
+                return held.pop()
+            clip = held[0].new_empty(held[0].shape[:2] + (n,) + held[0].shape[3:])
+            done = 0
+            while done < n:
+                piece = held.pop(0)
+                take = min(piece.shape[2], n - done)
+                clip[:, :, done:done + take] = piece[:, :, :take]
+                if take < piece.shape[2]:
+                    held.insert(0, piece[:, :, take:].clone())              # the next scene's first frames: less than a piece
+                done += take
+                del piece
+            return clip
+
+        for piece in pieces:
+            if piece.dim() != 5 or piece.shape[0] != 1 or piece.shape[1] != 3 or piece.shape[2] < 1:
+                raise ValueError(f"upscale_scenes_chunks: pieces of shape (1,3,n,h,w) expected, got {tuple(piece.shape)}")
+            if cutter is None:
+                cutter = SceneCutter(int(piece.shape[-2]) * int(piece.shape[-1]), **self._scene)
+            elif piece.shape[-2:] != last.shape[-2:]:
+                raise ValueError("upscale_scenes_chunks: the pieces differ in size")
+            with torch.no_grad(), E.device_guard(piece):
+                frames = piece[0].float() if last is None else torch.cat([last, piece[0].float()], dim=1)
+                hist, sad = ops.clip_scene_stats(frames.contiguous(), coefs)
+                skip = 0 if last is None else 1                             # the row of the frame carried over is not new
+                sad, hist = sad[skip:].cpu().numpy(), hist[skip:].cpu().numpy()
+                last = piece[0, :, -1:].float().clone()
+            del frames
+            held.append(piece)
+            self.frames += piece.shape[2]
+            del piece
+            for cut in cutter.push(sad, hist):
+                yield from upscale_clip_chunks(pipeline, scene_clip(cut), **kwargs)
+        if cutter is None:
+            raise ValueError("upscale_scenes_chunks: no frames")
+        for cut in cutter.finish() + [self.frames]:
+            if cut > base:
+                yield from upscale_clip_chunks(pipeline, scene_clip(cut), **kwargs)
+
+
+def upscale_scenes_chunks(pipeline, pieces, *, scene=(SCENE_THRESHOLD, SCENE_MIN_LEN, 0), **kwargs) -> SceneChunks:
+    """`upscale_clip_chunks`, scene by scene (`--scenes auto`).  `pieces`: an iterator of (1,3,n,h,w) clips on the device, in
+    order — a video read as far as it is needed; `scene` = (threshold, min_len, max_len) of `scene_cuts`; every other keyword is
+    `upscale_clip_chunks`' and goes to it unchanged.  Each piece's statistics (`ops.clip_scene_stats`, with the last frame of the
+    piece before in front) go to a `SceneCutter`; once a scene's end is certain, or the input ends, its frames are concatenated
+    and `upscale_clip_chunks` runs on them as on a clip of its own — flows, DDIM loop and tiles per scene, nothing temporal
+    crosses a cut — with the ONE `generator`, which carries on from scene to scene as it does from tile to tile; the scene's
+    frames are dropped before more input is pulled.  Yields exactly what `upscale_clip_chunks` yields, scene after scene: a clip
+    without a cut gives the chunks of `upscale_clip_chunks` on the whole clip bit for bit.  Held at once: the frames of the
+    scene that is open (at most `max_len` when given) plus the piece that closed it and the min_len frames of look-ahead.
+    The result iterates and records `.scenes` / `.frames` (`SceneChunks`)."""
+    return SceneChunks(pipeline, pieces, scene, kwargs)
