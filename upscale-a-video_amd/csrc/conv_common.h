@@ -27,6 +27,7 @@
 // This header: what the kernel families share — launch arguments, the gather helpers, the epilogues.  One translation unit per family
 // (round 6, VERDICT r5 #12: a k-step edit recompiles its own family, not the whole library):
 //   conv_gemm128.hip   conv_gemm_kernel<SMALL>           128 x 128 tile (small grids, the 4- / 8-channel layers)
+//   conv_thin.hip      conv_thin_kernel<KS, OF32>        n <= 16 output channels: haloed pixel patch staged once, 16-wide MFMA tile
 //   conv_gemm256i.hip  conv_gemm256i_kernel<6, GNK>      256 x 256 tile, 8 waves, rotated k-step (nearest-2x gather, A/B reference of the bit-identity tests)
 //   conv_gemm256w.hip  conv_gemm256w_kernel<GNK>         256 x 256 tile, FOUR waves (the product kernel: every big-tile launch)
 //   conv_gemm_dev.hip  round-1 family, round 2-3 loop + LayerNorm-fold instances, short-K kernel, stamped four-wave instance — compiled
@@ -78,6 +79,7 @@ struct ConvArgs {
 
 // ---- launch functions of the kernel families (one translation unit each; grid = workgroups, gn_mode = gn_mode_of(cpg_log2) or 0) ----
 int conv_launch_tile128(const ConvArgs& a, long long grid, bool small, hipStream_t s);
+int conv_launch_thin(const ConvArgs& a, hipStream_t s);       // conv_thin.hip: n <= 16, one 16-wide MFMA column tile (selection: conv_thin_ok, conv_gemm.hip)
 int conv_launch_wave8(const ConvArgs& a, long long grid256, int gn_mode, hipStream_t s);
 int conv_launch_wave4(const ConvArgs& a, long long grid256, int gn_mode, bool hilo, hipStream_t s);
 #ifdef UAV_DEV_KERNELS

@@ -28,6 +28,20 @@ const ConvEnv& conv_env() {
     }();
     return env;
 }
+// Thin kernel (conv_thin.hip): plain stride-1 (1,k,k) convs, k = 1 | 3, with at most 16 output channels and one fp16 source — bias and
+// scale only, result fp32 or fp16.  Everything else (residual, time-embedding rows, statistics, activations, out_map, ...) keeps its path.
+// UAV_CONV_THIN=0 restores the 128 x 128 tile for the A/B; unlike the switches above it is read at every ELIGIBLE launch (one per UNet
+// forward / decode chunk), so that one process can run both paths on the same inputs (tests/test_conv_thin_gpu.py).
+bool conv_thin_ok(const uav_conv_params* q) {
+    if (q->n > 16 || q->c2 != 0 || q->a2 || q->a2_images || q->a2_center_tap || (q->c1 % 64) || q->c1 <= 0) return false;
+    if (q->kt != 1 || q->pad_t != 0 || q->stride != 1 || q->upsample || q->kh != q->kw || (q->kh != 1 && q->kh != 3)) return false;
+    if (q->pad_h < 0 || q->pad_w < 0 || q->pad_h > 4 || q->pad_w > 4) return false;
+    if (q->flags & ~(UAV_CONV_OUT_F32 | UAV_CONV_NO_SHORTK | UAV_CONV_NO_W4)) return false;
+    if (q->residual || q->rowbias || q->gn_partials || q->out_map_w || q->ln_raw_out || q->ln_stat_in) return false;
+    if ((long long)q->kh * q->kw * q->c1 != q->k_pad || (long long)q->hi * q->wi * q->c1 >= (1ll << 31)) return false;
+    const char* e = getenv("UAV_CONV_THIN");
+    return !(e && atoi(e) == 0);
+}
 // tile selection: the 256x256 kernel needs n_pad % 256 == 0 and enough tiles to fill 256 CUs
 bool conv_uses_big_tile(const uav_conv_params* q) {
     const bool small = (q->c1 == 8 && q->c2 == 0);
@@ -276,5 +290,6 @@ extern "C" int uav_conv_gemm_f16(const uav_conv_params* q, void* stream) {
 #endif
         return conv_launch_wave8(a, grid256, gnm, s);
     }
+    if (!small && conv_thin_ok(q)) return conv_launch_thin(a, s);
     return conv_launch_tile128(a, grid, small, s);
 }

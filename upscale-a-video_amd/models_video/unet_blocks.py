@@ -85,10 +85,13 @@ class CrossAttnDownBlock3D(nn.Module):
                                                         padding=downsample_padding, name="op")]) if add_downsample else None
         self.gradient_checkpointing = False
 
-    def run(self, x, g, temb, ehs_rows, n_text):
+    def run(self, x, g, temb, ehs_rows, n_text, first_resnet_done=False):
+        """first_resnet_done: `x` is already the output of resnets[0] (the text-free front of the block, which the
+        CFG-shared UNet head evaluates once for both batch entries): start at the first transformer."""
         outs = []
-        for resnet, attn in zip(self.resnets, self.attentions):
-            x = resnet.run(x, g, temb)
+        for i, (resnet, attn) in enumerate(zip(self.resnets, self.attentions)):
+            if i or not first_resnet_done:
+                x = resnet.run(x, g, temb)
             x = attn.run(x, g, ehs_rows, n_text)
             outs.append((x, g))
         if self.downsamplers is not None:

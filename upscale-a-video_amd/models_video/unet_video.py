@@ -279,6 +279,7 @@ class UNetVideoModel(ModelMixin, ConfigMixin, E.EngineModule):
         # text differs, so everything ahead of the first text-conditioned block is computed once and duplicated
         # (bit-identical to running it twice; the pipeline sets `cfg_shared_input`, default off).
         first = 0
+        front_done = False
         if cfg_shared_input and bsz == 2 and not getattr(self.down_blocks[0], "has_cross_attention", True):
             rows1 = g.rows // 2
             g1 = E.Geom(1, g.t, g.h, g.w)
@@ -290,13 +291,21 @@ class UNetVideoModel(ModelMixin, ConfigMixin, E.EngineModule):
             x1 = self.down_temp_blocks[0].run(x1, g1, emb1)
             # the skips stay single: their consumers (GroupNorm and convs with a second source) read them batch-broadcast
             skips = [((s_ if BROADCAST_SKIPS else torch.cat([s_, s_])), E.Geom(2, sg.t, sg.h, sg.w)) for (s_, sg) in skips1]
+            # the first ResNet of a cross-attention block sees no text either: only the transformer after it does, so it
+            # belongs to the shared head (its statistics partials are duplicated with its rows)
+            if len(self.down_blocks) > 1 and isinstance(self.down_blocks[1], CrossAttnDownBlock3D):
+                x1 = self.down_blocks[1].resnets[0].run(x1, g1, emb1)
+                front_done = True
             x, g = ops.duplicate_rows(x1), E.Geom(2, g1.t, g1.h, g1.w)
             first = 1
         else:
             x = self.conv_in.run(x, g, out_f32=s32)
             skips = [(x, g)]
-        for blk, tblk in list(zip(self.down_blocks, self.down_temp_blocks))[first:]:
-            x, g, outs = blk.run(x, g, emb, ehs_rows, n_text)
+        for i, (blk, tblk) in enumerate(list(zip(self.down_blocks, self.down_temp_blocks))[first:]):
+            if front_done and i == 0:
+                x, g, outs = blk.run(x, g, emb, ehs_rows, n_text, first_resnet_done=True)
+            else:
+                x, g, outs = blk.run(x, g, emb, ehs_rows, n_text)
             skips.extend(outs)
             x = tblk.run(x, g, emb)
         x = self.mid_block.run(x, g, emb, ehs_rows, n_text)
