@@ -166,8 +166,8 @@ int uav_conv_gemm_hilo_ok(const uav_conv_params* p);
  * 366,377,467,478,495; unet_video.py:567) and on per-frame 4-D tensors (attention.py:374;
  * unet_blocks.py:740) followed by SiLU (resnet.py:268,284).
  *   x: fp16 (or fp32, x_f32 = 1) rows [n_inst*rows_per_inst][c] read from up to two channel-concatenated sources.
- *   stats pass : partial per-channel (sum, sumsq) -> scale/shift tables [n_inst][c] (fp32):
- *                scale = gamma*rstd, shift = beta - mean*rstd*gamma.
+ *   stats pass : per chunk of rows and group (sum, sum of squares about the chunk's mean), merged in fp64 -> scale/shift
+ *                tables [n_inst][c] (fp32): scale = gamma*rstd, shift = beta - mean*scale.
  *   apply pass : y = act(x*scale + shift), fp16, written contiguously [rows][c1+c2].
  */
 int64_t uav_groupnorm_workspace_bytes(int32_t n_inst, int32_t c);

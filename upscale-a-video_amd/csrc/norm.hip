@@ -6,9 +6,9 @@
 // kernel here: an "instance" is a run of `rows_per_inst` consecutive channels-last rows
 // (T*H*W rows, or H*W rows for the per-frame flavour).
 //
-// Pass 1 (HBM-bound, reads x once = 2 B/element): per-(instance, chunk) per-channel fp32
-// (sum, sumsq) partials.  Pass 2 (tiny): fp64 reduction over chunks and the channels of each
-// group -> per-(instance, channel) fp32 scale = gamma*rstd, shift = beta - mean*rstd*gamma.
+// Pass 1 (HBM-bound, reads x once = 2 B/element): per-(instance, chunk, group) fp32 triples
+// (sum as hi + lo, sum of squares about the chunk's mean), see gn_partial_kernel.  Pass 2 (tiny): fp64
+// merge over chunks -> per-(instance, channel) fp32 scale = gamma*rstd, shift = beta - mean*scale.
 // Pass 3 (HBM-bound, 2 B read + 2 B written per element): y = act(x*scale + shift).
 // The input may be two channel-concatenated tensors (skip connections, unet_blocks.py:563):
 // groups may straddle the seam (1536 channels / 32 groups = 48), which per-channel partials
@@ -45,10 +45,18 @@ UAV_DEVINL void gn_load8(const GnSrc& s, long long row, int v, float (&f)[8]) {
     }
 }
 
+// Sums of x and x*x in fp32 lose the variance of data whose mean is large against its spread (0.8 +- 1e-3: the sum of
+// squares is 0.64 n, the variance 3e-7).  So a chunk sums DEVIATIONS: every channel takes the chunk's first row as its
+// pivot p and accumulates S = sum(x - p), Q = sum((x - p)^2) in fp32 (16 rows per thread where the chunk count is not
+// capped, hundreds where it is: the sums are of deviations either way), which gives the channel's mean p + S/n and its
+// sum of squares about that mean, Q - S*S/n, without cancellation; the row lanes and the
+// channels of a group are merged in fp64 (Chan et al.).  A chunk hands on, per group, three floats: its sum as hi + lo and
+// M2, its sum of squares about its own mean.
 template <bool F32, int U>
 __global__ __launch_bounds__(256) void gn_partial_kernel(GnSrc s, long long rows_per_inst, int chunks, int c_real, int groups,
                                                          float* __restrict__ ws) {
-    __shared__ float red[256 * 16];
+    __shared__ double lds[3 * 1024];                  // 256 x 16 floats of partials, then c doubles (means) + c floats (M2)
+    float* red = (float*)lds;
     const int c = s.c1 + s.c2, cvec = c >> 3;
     const int rpp = 256 / cvec;                       // rows per pass (>=1, cvec <= 256)
     const int tid = threadIdx.x;
@@ -58,10 +66,12 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(GnSrc s, long long rows
     const long long rows_per_chunk = (rows_per_inst + chunks - 1) / chunks;
     const long long r0 = (long long)chunk * rows_per_chunk;
     long long r1 = r0 + rows_per_chunk; if (r1 > rows_per_inst) r1 = rows_per_inst;
-    float sm[8], sq[8];
+    const long long nrows = r1 > r0 ? r1 - r0 : 0;    // a capped chunk count can leave the last chunks empty
+    float sm[8], sq[8], pv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sm[j] = 0.f; sq[j] = 0.f; }
-    if (active) {
+    for (int j = 0; j < 8; ++j) { sm[j] = 0.f; sq[j] = 0.f; pv[j] = 0.f; }
+    if (active && nrows) {
+        gn_load8<F32>(s, inst * rows_per_inst + r0, v, pv);
         // U independent 16-B loads in flight per thread
         for (long long r = r0 + ro; r < r1; r += (long long)rpp * U) {
             float x[U][8];
@@ -71,46 +81,59 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(GnSrc s, long long rows
                 if (rr < r1) gn_load8<F32>(s, inst * rows_per_inst + rr, v, x[u]);
                 else {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) x[u][j] = 0.f;
+                    for (int j = 0; j < 8; ++j) x[u][j] = pv[j];
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { float f = x[u][j]; sm[j] += f; sq[j] += f * f; }
+                for (int j = 0; j < 8; ++j) { float f = x[u][j] - pv[j]; sm[j] += f; sq[j] += f * f; }
         }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { red[tid * 16 + j] = sm[j]; red[tid * 16 + 8 + j] = sq[j]; }
     __syncthreads();
-    float a[16];
+    double a[16];
     if (tid < cvec) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            a[j] = 0.f;
-            for (int q = 0; q < rpp; ++q) a[j] += red[(q * cvec + tid) * 16 + j];
+            a[j] = 0.0;
+            for (int q = 0; q < rpp; ++q) a[j] += (double)red[(q * cvec + tid) * 16 + j];
         }
     }
     __syncthreads();
-    // per-channel totals of this chunk -> LDS [0:c] sums, [c:2c] sums of squares, then one (sum, sumsq) pair per GROUP:
-    // the finalize pass reads chunks x 2 floats per group instead of chunks x 2 x (C/G) (it was a third of the statistics
-    // time at 2048 chunks: 36 us per launch)
-    if (tid < cvec) {
+    // per-channel mean and M2 of this chunk -> LDS, then one (sum hi, sum lo, M2) triple per GROUP: the finalize pass reads
+    // chunks x 3 floats per group instead of chunks x 2 x (C/G) (it was a third of the statistics time at 2048 chunks)
+    float* m2s = red + 2 * c;
+    if (tid < cvec) {                                 // thread tid < cvec has v = tid: its pv are this vector's pivots
+        const double inv_n = nrows ? 1.0 / (double)nrows : 0.0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { red[tid * 8 + j] = a[j]; red[c + tid * 8 + j] = a[8 + j]; }
+        for (int j = 0; j < 8; ++j) {
+            const double d = a[j] * inv_n, m2 = a[8 + j] - a[j] * d;
+            lds[tid * 8 + j] = (double)pv[j] + d; m2s[tid * 8 + j] = m2 > 0.0 ? (float)m2 : 0.f;
+        }
     }
     __syncthreads();
     const int cpg = c_real / groups;
-    float* dst = ws + (long long)(inst * chunks + chunk) * 2 * groups;
+    float* dst = ws + (long long)(inst * chunks + chunk) * 3 * groups;
     for (int g = tid; g < groups; g += 256) {
-        float gs = 0.f, gq = 0.f;
-        for (int k = 0; k < cpg; ++k) { gs += red[g * cpg + k]; gq += red[c + g * cpg + k]; }
-        dst[g] = gs; dst[groups + g] = gq;
+        double gs = 0.0;
+        for (int k = 0; k < cpg; ++k) gs += lds[g * cpg + k];
+        const double mg = gs / cpg;
+        double m2 = 0.0;
+        for (int k = 0; k < cpg; ++k) {
+            const double dm = lds[g * cpg + k] - mg;
+            m2 += (double)m2s[g * cpg + k] + (double)nrows * dm * dm;
+        }
+        const double sum = (double)nrows * gs;
+        const float hi = (float)sum;
+        dst[g] = hi; dst[groups + g] = (float)(sum - (double)hi); dst[2 * groups + g] = (float)m2;
     }
 }
 
-// One workgroup per (group, instance): fp64 reduction of the per-chunk (sum, sumsq) pairs of the group, then scale/shift
-// for its channels.
+// One workgroup per (group, instance): fp64 merge of the per-chunk (sum, M2) of the group, then scale/shift for its
+// channels.  shift is formed from the fp32 scale the apply pass multiplies by, so y = scale * (x - mean) + beta holds to the
+// rounding of the shift itself.
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ ws, int chunks, int c, int c_real,
                                                           int groups, long long rows_per_inst, float eps,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -118,27 +141,41 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     __shared__ double rs[256], rq[256];
     const int g = blockIdx.x, inst = blockIdx.y, tid = threadIdx.x;
     const int cpg = c_real / groups;
-    const float* base = ws + (long long)inst * chunks * 2 * groups;
-    double a = 0.0, b = 0.0;
-    for (int k = tid; k < chunks; k += 256) {
-        a += base[(long long)k * 2 * groups + g];
-        b += base[(long long)k * 2 * groups + groups + g];
-    }
-    rs[tid] = a; rq[tid] = b;
+    const float* base = ws + (long long)inst * chunks * 3 * groups;
+    const long long rows_per_chunk = (rows_per_inst + chunks - 1) / chunks;
+    double a = 0.0;
+    for (int k = tid; k < chunks; k += 256)
+        a += (double)base[(long long)k * 3 * groups + g] + (double)base[(long long)k * 3 * groups + groups + g];
+    rs[tid] = a;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { rs[tid] += rs[tid + o]; rq[tid] += rq[tid + o]; }
+        if (tid < o) rs[tid] += rs[tid + o];
         __syncthreads();
     }
     const double n = (double)rows_per_inst * cpg;
     const double mean = rs[0] / n;
-    double var = rq[0] / n - mean * mean; if (var < 0.0) var = 0.0;
-    const float fm = (float)mean, fr = (float)(1.0 / sqrt(var + (double)eps));
+    double b = 0.0;
+    for (int k = tid; k < chunks; k += 256) {
+        long long rk = rows_per_inst - (long long)k * rows_per_chunk; if (rk > rows_per_chunk) rk = rows_per_chunk;
+        if (rk <= 0) continue;
+        const double nk = (double)rk * cpg;
+        const float* p = base + (long long)k * 3 * groups;
+        const double dm = ((double)p[g] + (double)p[groups + g]) / nk - mean;
+        b += (double)p[2 * groups + g] + nk * dm * dm;
+    }
+    rq[tid] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) rq[tid] += rq[tid + o];
+        __syncthreads();
+    }
+    const double rstd = 1.0 / sqrt(rq[0] / n + (double)eps);
     for (int j = tid; j < cpg; j += 256) {
         const int ch = g * cpg + j;
         const float ga = gamma ? gamma[ch] : 1.f, be = beta ? beta[ch] : 0.f;
-        scale[(long long)inst * c + ch] = ga * fr;
-        shift[(long long)inst * c + ch] = be - fm * fr * ga;
+        const float sc = (float)((double)ga * rstd);
+        scale[(long long)inst * c + ch] = sc;
+        shift[(long long)inst * c + ch] = (float)((double)be - mean * (double)sc);
     }
     // padding channels (c_real <= ch < c) carry scale = shift = 0
     if (g == 0)
@@ -261,10 +298,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnSrc s, long long rows_p
     }
 }
 
-// LayerNorm: one wave per row, row held in registers (c <= 2048), two-pass mean/variance.  (Round 3 tried hoisting gamma / beta
-// out of the row loop and prefetching the next row: 196 -> 228 ms per clip, dropped — the extra registers cost occupancy, and the
-// in-order vmcnt puts the prefetch's wait in front of the store anyway.)  F32: the rows are the fp32
-// residual stream (UNet stream_dtype = float32); the output is always the fp16 MFMA operand of the projection that follows.
+// LayerNorm: one wave per row, row held in registers (c <= 2048) as deviations from its first element, two-pass
+// mean/variance.  (Round 3 tried hoisting gamma / beta out of the row loop and prefetching the next row: 196 -> 228 ms per
+// clip, dropped — the extra registers cost occupancy, and the in-order vmcnt puts the prefetch's wait in front of the store
+// anyway.)  F32: the rows are the fp32 residual stream (UNet stream_dtype = float32); the output is always the fp16 MFMA
+// operand of the projection that follows.
 template <int NV, bool F32>
 __global__ __launch_bounds__(256) void layernorm_kernel(const char* __restrict__ x, char* __restrict__ y,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -290,11 +328,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const char* __restrict__
 #pragma unroll
                     for (int j = 0; j < 8; ++j) xv[i][j] = (float)h[j];
                 }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) s += xv[i][j];
             }
         }
-        const float mean = wave_sum(s) / (float)c;
+        // the row is held as deviations from its first element: their fp32 sum rounds against the row's spread, not against
+        // its mean (a constant fp32 row gave x - mean != 0 and an output off beta by 1e-7 * rsqrt(eps))
+        const float piv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, xv[0][0])));
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            if (lane + i * 64 < cvec) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { xv[i][j] -= piv; s += xv[i][j]; }
+            }
+        }
+        const float mean = wave_sum(s) / (float)c;        // of the deviations
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -355,8 +401,12 @@ extern "C" int uav_groupnorm_scale_shift(const void* x1, const void* x2, int32_t
     if (c1 <= 0 || c2 < 0 || (c1 % 8) || (c2 % 8) || c > 2048 || (c2 > 0 && !x2)) return UAV_ESHAPE;
     if (c_real <= 0 || c_real > c || groups <= 0 || (c_real % groups) || n_inst <= 0 || rows_per_inst <= 0) return UAV_ESHAPE;
     if (n_inst > 65535) return UAV_ESHAPE;
-    const int chunks = gn_chunks(n_inst, rows_per_inst, c);
-    if (workspace_bytes < (int64_t)n_inst * chunks * groups * 2 * 4) return UAV_EINVAL;
+    int chunks = gn_chunks(n_inst, rows_per_inst, c);
+    // three floats per (chunk, group); with one channel per group and the largest chunk count that would pass what
+    // uav_groupnorm_workspace_bytes promises (2 c floats per chunk), so the chunk count gives way
+    const long long fit = (long long)(gn_variant() == 0 ? 512 : GN_MAX_CHUNKS) * 2 * c / (3ll * groups);
+    if (chunks > fit) chunks = (int)fit;
+    if (workspace_bytes < (int64_t)n_inst * chunks * groups * 3 * 4) return UAV_EINVAL;
     if (groups > 2048) return UAV_ESHAPE;
     if (x2_rows && (c2 <= 0 || x2_rows * 2 != (int64_t)n_inst * rows_per_inst)) return UAV_ESHAPE;
     GnSrc s{(const char*)x1, (const char*)x2, c1, c2, (long long)x2_rows};
