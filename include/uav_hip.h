@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define UAV_ABI_VERSION 12
+#define UAV_ABI_VERSION 13
 
 #define UAV_EINVAL   (-1)   /* bad argument (null pointer, size not supported) */
 #define UAV_EALIGN   (-2)   /* pointer / stride alignment requirement violated */
@@ -642,6 +642,20 @@ int uav_clip_to_yuv420_sited(const float* frames_tchw, void* y, void* cb, void* 
  * memset or launch.  A memset or the launch that fails returns its hipError_t, positive, as every failed launch of this ABI does. */
 int uav_clip_scene_stats(const float* clip_cthw, int32_t t_len, int32_t h, int32_t w, int32_t* hist, int64_t* sad,
                          const int32_t* coefs, void* stream);
+
+/* Cross-fade of two renderings of the same frames (the front end's `--scene-overlap`; csrc/frame_axpby.hip): a per-frame weighted
+ * sum of two contiguous fp32 frame stacks [t_len][frame_elems] in one launch, every output defined bit for bit.  `wa`, `wb`: device
+ * arrays of t_len floats.
+ *   out[t][i] = wa[t] * a[t][i] + wb[t] * b[t][i]        for t < t_len, i < frame_elems
+ * Both products are rounded to fp32 and then added — no fused multiply-add, unlike uav_axpby_f32, whose scalar weights the
+ * compiler may fuse —, which is numpy's float32 expression.  16-byte loads and stores when a, b and out are 16-byte aligned and
+ * frame_elems % 4 == 0, scalar accesses otherwise, same bits.  `out` may be exactly `a` or exactly `b` (in place); any other
+ * overlap between `out` and an input is the caller's error and leaves the overlapping frames undefined.  Nothing outside
+ * out[0 .. t_len*frame_elems) is written.  A null pointer: UAV_EINVAL; t_len <= 0, t_len > 65535, frame_elems <= 0 or more than
+ * 2^32 - 1 threads along a grid dimension (frame_elems beyond 2^35 - 2048): UAV_ESHAPE; a pointer that is not 4-byte aligned:
+ * UAV_EALIGN — all before any launch. */
+int uav_frame_axpby_f32(const float* a, const float* b, float* out, const float* wa, const float* wb, int32_t t_len,
+                        int64_t frame_elems, void* stream);
 
 #ifdef __cplusplus
 }

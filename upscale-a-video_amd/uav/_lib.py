@@ -93,6 +93,7 @@ SIGNATURES = {
     "uav_yuv420_sited_to_clip_f32": (C.c_int, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, C.POINTER(i32), c_p]),
     "uav_clip_to_yuv420_sited": (C.c_int, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, C.POINTER(i32), c_p]),
     "uav_clip_scene_stats": (C.c_int, [c_p, i32, i32, i32, c_p, c_p, C.POINTER(i32), c_p]),
+    "uav_frame_axpby_f32": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i32, i64, c_p]),
     "uav_groupnorm_finalize_partials2": (C.c_int, [c_p, i64, i32, i32, i32, c_p, i64, i32, i32, i32, i32, i32, i64, i32, f32, c_p, c_p, c_p, c_p, c_p]),
     "uav_groupnorm_apply": (C.c_int, [c_p, c_p, i32, i32, i32, i64, i32, i64, c_p, c_p, i32, c_p, c_p, i32, c_p]),
     "uav_layernorm_f16": (C.c_int, [c_p, c_p, c_p, c_p, i64, i32, f32, c_p]),
@@ -142,7 +143,7 @@ SIGNATURES = {
     "uav_propagate_step_f32": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i64, i64, i32, f32, f32, f32, c_p]),
 }
 
-EXPECTED_ABI = 12        # include/uav_hip.h UAV_ABI_VERSION this binding was written against
+EXPECTED_ABI = 13        # include/uav_hip.h UAV_ABI_VERSION this binding was written against
 
 
 class UavError(RuntimeError):

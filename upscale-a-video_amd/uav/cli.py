@@ -26,8 +26,10 @@ written (`C420mpeg2`, `C420p10`), a (1,2,1) filter around the even column (`uav_
 `replicate`, keeps every file's bytes as they were. `--scenes auto` splits a video at its cuts: `uav_clip_scene_stats` makes per
 frame a luma histogram and the absolute difference to the frame before on the GPU, `video_io.scene_cuts` decides on the host
 (`--scene-threshold MAD:HIST`, `--scene-min N`, `--scene-max N`; the defaults are conventional starting values, NOT validated on
-real footage), and every scene goes through `video_io.upscale_clip_chunks` as a clip of its own, one after the other into the
-one output file, so that no temporal window, attention or flow crosses a cut; a `.y4m` input, file or pipe, is then read 48
+real footage; `--scene-overlap K` runs both sides of a split that `--scene-max` forced over K shared frames and cross-fades them
+with `uav_frame_axpby_f32` — a linear dissolve between two independent renderings, which softens detail over K frames and does
+not remove their difference, judged on no real footage; detected cuts stay hard), and every scene goes through
+`video_io.upscale_clip_chunks` as a clip of its own, one after the other into the one output file, so that no temporal window, attention or flow crosses a cut; a `.y4m` input, file or pipe, is then read 48
 frames at a time and only as far as the scene at hand needs (`video_io.Y4MReader`), which bounds the memory by the longest scene
 or `--scene-max` instead of the video. Without it (`--scenes off`, the default) the input is read whole and the video is one
 clip, byte for byte as before. `-i` may also be a directory whose `.y4m` / `.npy` files and image sub-directories are one video
@@ -112,6 +114,10 @@ def build_parser():
                         "--scene-* values are checked whether or not --scenes auto is given")
     p.add_argument("--scene-max", dest="scene_max", metavar="N", default="0",
                    help="with --scenes auto: split a scene after N frames even without a cut, which bounds the memory; 0 (default) = never")
+    p.add_argument("--scene-overlap", dest="scene_overlap", metavar="K", default="0",
+                   help="with --scenes auto and --scene-max: run both sides of a forced split over K shared frames and cross-fade them "
+                        "(a linear dissolve between two renderings, NOT judged on real footage); at most --scene-min; 0 (default) = "
+                        "hard splits, the files' bytes as ever; detected cuts always stay hard")
     p.add_argument("--seed", type=int, default=10)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of the output (default: the input's, 24 when it has none)")
@@ -141,7 +147,8 @@ def _out_size_options(args):
 
 
 def _scene_options(args):
-    """`--scene-threshold` / `--scene-min` / `--scene-max` as `video_io.upscale_scenes_chunks` takes them: ((MAD, HIST), min, max)."""
+    """`--scene-threshold` / `--scene-min` / `--scene-max` / `--scene-overlap` as `video_io.upscale_scenes_chunks` takes them:
+    (((MAD, HIST), min, max), overlap)."""
     import math
     parts = args.scene_threshold.split(":")
     try:
@@ -159,7 +166,12 @@ def _scene_options(args):
         raise UserError(f"--scene-min: at least 1 frame expected, got {args.scene_min!r}")
     if 0 < counts[1] < counts[0]:
         raise UserError(f"--scene-max: 0 (never force a split) or at least --scene-min = {counts[0]} expected, got {args.scene_max!r}")
-    return (mad, dist), counts[0], counts[1]
+    text = args.scene_overlap
+    if not (text.isascii() and text.isdigit()):
+        raise UserError(f"--scene-overlap: a number of frames expected, got {text!r}")
+    if int(text) > counts[0]:
+        raise UserError(f"--scene-overlap: at most --scene-min = {counts[0]} frames expected, got {text!r}")
+    return ((mad, dist), counts[0], counts[1]), int(text)
 
 
 class _Pieces:
@@ -293,7 +305,7 @@ def _read(path):
 def run(args):
     from . import tiling, video_io
     size, scale = _out_size_options(args)
-    scene = _scene_options(args)
+    scene, overlap = _scene_options(args)
     auto = args.scenes == "auto"
     videos = ["-"] if args.input_path == "-" else list_videos(args.input_path)
     if args.y4m_out is not None and len(videos) > 1:
@@ -347,7 +359,8 @@ def run(args):
                        coefs=None if need_frames else coefs, fmt=fmt,
                        out_size=None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w), chroma=args.chroma)
         if auto:        # scene by scene, the input read piece by piece as the scenes need it
-            chunks = video_io.upscale_scenes_chunks(pipeline, source.clips(device, args.matrix, args.chroma), scene=scene, **options)
+            chunks = video_io.upscale_scenes_chunks(pipeline, source.clips(device, args.matrix, args.chroma), scene=scene, overlap=overlap,
+                                                    **options)
         else:
             chunks = video_io.upscale_clip_chunks(pipeline, clip, **options)
         with video_io.Y4MWriter(sys.stdout.buffer if out_path == "-" else out_path, out_w, out_h, args.fps or fps or 24, full_range,
@@ -375,6 +388,8 @@ def run(args):
             scenes = f", {len(chunks.scenes)} scene(s)"
             if starts:
                 scenes += " (cuts at " + ", ".join(map(str, starts[:12])) + (", …" if len(starts) > 12 else "") + ")"
+            if chunks.seams:
+                scenes += f", {overlap}-frame overlap at {len(chunks.seams)} split(s)"
         print(f"[{index + 1}/{len(videos)}] {name}: {t} frames {in_size[0]}x{in_size[1]} -> {out_h}x{out_w}, {tiles} tile(s){scenes}, "
               f"{seconds:.2f} s -> {out_path}", file=sys.stderr if out_path == "-" else sys.stdout, flush=True)
     return out_path

@@ -1494,3 +1494,23 @@ def clip_scene_stats(clip, coefs):
     sad = torch.empty((t,), dtype=torch.int64, device=clip.device)
     _lib.check(lib.uav_clip_scene_stats(_p(clip), t, h, w, _p(hist), _p(sad), k, _stream()), "uav_clip_scene_stats")
     return hist, sad
+
+
+def frame_axpby_f32(a, b, wa, wb, out=None):
+    """out[t] = wa[t] * a[t] + wb[t] * b[t] for two contiguous fp32 frame stacks (T,...) of one shape on one GPU and fp32 weights
+    (T,) there: both products rounded to fp32, then added — numpy's float32 expression bit for bit (`uav_frame_axpby_f32`, one
+    launch).  Contiguous views are taken as they are, nothing is copied.  `out`: a tensor like `a`, which may be `a` or `b`
+    itself (in place; any other overlap is the caller's error); None allocates it.  Returns `out`."""
+    lib = _lib.load()
+    _req(a, torch.float32, "a")
+    if a.dim() < 1 or a.shape[0] < 1 or a.numel() == 0:
+        raise _lib.UavError(f"frame_axpby_f32: (T,...) frames expected, got {tuple(a.shape)}")
+    t = a.shape[0]
+    out = torch.empty_like(a) if out is None else out
+    for name, p, shape in (("b", b, a.shape), ("out", out, a.shape), ("wa", wa, (t,)), ("wb", wb, (t,))):
+        _req(p, torch.float32, name)
+        if p.shape != shape or p.device != a.device:
+            raise _lib.UavError(f"frame_axpby_f32: {name} must be fp32 of shape {tuple(shape)} on {a.device}, got {tuple(p.shape)} on {p.device}")
+    rc = lib.uav_frame_axpby_f32(_p(a), _p(b), _p(out), _p(wa), _p(wb), t, a.numel() // t, _stream())
+    _lib.check(rc, "uav_frame_axpby_f32")
+    return out

@@ -34,7 +34,11 @@ pipe that way, with `read_y4m`'s header parser and refusals —, gets each piece
 `SceneCutter`, the streaming form of the pure function `scene_cuts`, find the cuts, and runs `upscale_clip_chunks` on every
 scene as a clip of its own with one shared generator; nothing temporal crosses a cut and no more input is held than the open
 scene needs. The detector's defaults (`SCENE_THRESHOLD`, `SCENE_MIN_LEN`) are conventional starting values that have not been
-validated on real footage. Without it a video is one clip and is read whole.
+validated on real footage. Without it a video is one clip and is read whole.  `overlap=K` (`--scene-overlap`) cross-fades the
+splits that `max_len` forces in the middle of a shot: the scene before such a split runs K frames on, those K fp32 frames are
+held at the delivery size and blended with the next scene's first K by `ops.frame_axpby_f32` (csrc/frame_axpby.hip, every bit
+defined); detected cuts stay hard.  A linear dissolve between two independent renderings: it softens detail over K frames and
+does not remove their difference, and nobody has judged it on real footage.
 
 Compressed containers and codecs are not read or written, and there is no captioner (the reference's LLaVA step).
 """
@@ -540,7 +544,7 @@ def _window_to_planes(window, planes, dst, coefs, fmt=OUT_FORMATS["420"]):
 
 def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt, raft=None, propagation_steps=(), steps, guidance_scale,
                         noise_level, tile_size=256, perform_tile=False, color_fix="None", generator, coefs: YuvCoefs = None, fmt="420",
-                        out_size=None, chroma="replicate"):
+                        out_size=None, chroma="replicate", seam=None):
     """What the upscaling program does with one video between reading and writing it, in its order, 3 output frames at a time:
     bidirectional flows of the whole clip when propagation steps are asked for, then the DDIM loop of the whole clip — of
     every tile (`tiling.needs_tiling`: asked for, or h*w >= 384*384), or of the one pipeline call — whose results live at the
@@ -558,7 +562,12 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
 
     `chroma="sited"` with `coefs` of a left-sited 4:2:0 output (`output_siting(fmt, coefs.full_range, chroma)`): the 3-tap
     chroma filter crosses tile borders, so a chunk is assembled as fp32 frames too (the same branch) and converted by
-    `postprocess_planes(..., siting=...)`.  Every other case — 'replicate', 4:4:4, full-range 8-bit 4:2:0 — is unchanged."""
+    `postprocess_planes(..., siting=...)`.  Every other case — 'replicate', 4:4:4, full-range 8-bit 4:2:0 — is unchanged.
+
+    `seam` = (head, tail), for `SceneChunks`' cross-fade of forced splits: a chunk that holds one of the clip's first `head` or last
+    `tail` frames is yielded as fp32 frames (n,3,H,W) at the delivery size — assembled, colour-fixed and resized as above, NOT
+    converted — even when `coefs` is given; the caller blends and converts them.  Every other chunk, and every chunk when `seam` is
+    None, takes the path and gives the bytes described above."""
     from models_video import color_correction
     from . import tiling
     if color_fix not in ("None", "AdaIn", "Wavelet"):
@@ -570,6 +579,9 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     if propagation_steps and raft is None:
         raise ValueError("propagation steps need a flow estimator (raft=...)")
     h, w = clip.shape[-2:]
+    head, tail = (0, 0) if seam is None else (int(v) for v in seam)
+    if head < 0 or tail < 0 or head + tail > clip.shape[2]:
+        raise ValueError(f"seam = (head, tail) must lie within the clip's {clip.shape[2]} frames without overlapping, got {seam!r}")
     if out_size is not None:
         out_h, out_w = output_size(4 * h, 4 * w, out_size=(out_size[1], out_size[0]), fmt=fmt if coefs is not None else "444")
         out_size = None if (out_h, out_w) == (4 * h, 4 * w) else (out_h, out_w)
@@ -586,7 +598,8 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
     for start, n, pieces in chunks:
         with torch.no_grad(), E.device_guard(clip):
             window = None
-            if coefs is not None and color_fix == "None" and out_size is None and siting is None:
+            at_seam = start < head or start + n > clip.shape[2] - tail
+            if coefs is not None and color_fix == "None" and out_size is None and siting is None and not at_seam:
                 out = _new_planes(clip, n, 4 * h, 4 * w, fmt)
                 for dst, window in pieces:
                     _window_to_planes(window, out, dst, coefs, fmt)
@@ -603,7 +616,7 @@ def upscale_clip_chunks(pipeline, clip: torch.Tensor, *, prompt, negative_prompt
                     out = fix(out, source).float()
                 if out_size is not None:
                     out = ops.resize_aa_f32(out.contiguous(), *out_size)
-                if coefs is not None:
+                if coefs is not None and not at_seam:
                     out = postprocess_planes(out, coefs, fmt, siting)
             del pieces, window                                  # views of the decoder's output: let it go before the next decode
         yield out
@@ -632,7 +645,9 @@ class SceneCutter:
     """The decision of `scene_cuts`, fed piece by piece: `push(sad, hist)` takes the statistics of the next frames (sad[i] against
     the frame before, whichever piece that was in; the very first frame's is ignored) and returns the cuts that are certain by
     now, as absolute frame indices; `finish()` returns those the end of the input decides.  All cuts, in order, are in `.cuts`:
-    the same list as one `scene_cuts(..., final=True)` call on the whole arrays, however the input was cut into pieces."""
+    the same list as one `scene_cuts(..., final=True)` call on the whole arrays, however the input was cut into pieces.  `.forced`
+    is the sub-list of the cuts that `max_len` produced: a split in the middle of a shot, where `--scene-overlap` cross-fades.  A
+    cut that is also a detected candidate — the earliest one falling on start + max_len — counts as detected."""
 
     def __init__(self, pixels: int, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MIN_LEN, max_len=0):
         self.mad_min, self.hist_min = (float(v) for v in threshold)
@@ -642,7 +657,7 @@ class SceneCutter:
                              f"{pixels!r}, {min_len!r}, {threshold!r}")
         if self.max_len < 0 or 0 < self.max_len < self.min_len:
             raise ValueError(f"max_len must be 0 (never force a split) or at least min_len = {self.min_len}, got {max_len!r}")
-        self.frames, self.cuts = 0, []
+        self.frames, self.cuts, self.forced = 0, [], []
         self._start, self._pending, self._last_hist = 0, [], None
 
     def push(self, sad, hist):
@@ -679,12 +694,14 @@ class SceneCutter:
                 # every later one is too near the end
                 break
             new.append(t)
+            if self._pending[:1] != [t]:
+                self.forced.append(t)                   # no candidate here: max_len alone made this cut
             self._start = t
         self.cuts.extend(new)
         return new
 
 
-def scene_cuts(sad, hist, pixels, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MIN_LEN, max_len=0, final=True):
+def scene_cuts(sad, hist, pixels, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MIN_LEN, max_len=0, final=True, forced=False):
     """The first frames of the scenes 2, 3, ... of a clip of T frames, from `ops.clip_scene_stats`' integers `sad` (T,) and `hist`
     (T,64) and `pixels` = h*w.  For t >= 1, in float64: mad[t] = sad[t] / pixels (8-bit luma steps) and hd[t] = sum_b |hist[t][b] -
     hist[t-1][b]| / (2 pixels) in [0, 1]; frame t is a candidate iff mad[t] >= M AND hd[t] >= D, `threshold` = (M, D) — fast motion
@@ -693,24 +710,29 @@ def scene_cuts(sad, hist, pixels, *, threshold=SCENE_THRESHOLD, min_len=SCENE_MI
     with a neighbour.  `max_len` = N > 0 forces a split at s + N when no cut fell in (s, s + N], under the same rule for the tail.
     `final=False`: T is what has been seen so far and more may follow — only the cuts that min_len known further frames make
     certain are returned, which is the same rule for the tail: both forms give one list for the same arrays, and a longer
-    input only appends to it (`SceneCutter` is this form with a memory).  The defaults are conventional starting values and have NOT
-    been validated on real footage."""
+    input only appends to it (`SceneCutter` is this form with a memory).  `forced=True`: the pair (cuts, forced cuts) instead — the
+    second list holds those of the first that `max_len` alone produced (`SceneCutter.forced`).  The defaults are conventional
+    starting values and have NOT been validated on real footage."""
     cutter = SceneCutter(pixels, threshold=threshold, min_len=min_len, max_len=max_len)
     cutter.push(sad, hist)
     if final:
         cutter.finish()
-    return list(cutter.cuts)
+    return (list(cutter.cuts), list(cutter.forced)) if forced else list(cutter.cuts)
 
 
 class SceneChunks:
     """The iterator `upscale_scenes_chunks` returns: the chunks of scene after scene; `.scenes` is the list of (start, end) frame
-    ranges of the scenes begun so far and `.frames` the number of input frames pulled."""
+    ranges of the scenes begun so far — the nominal ranges [c_i, c_i+1) between the cuts, whatever `overlap` is —, `.seams` the
+    forced cuts that have been cross-faded so far and `.frames` the number of input frames pulled."""
 
-    def __init__(self, pipeline, pieces, scene, kwargs):
+    def __init__(self, pipeline, pieces, scene, kwargs, overlap=0):
         threshold, min_len, max_len = scene
-        self.scenes, self.frames = [], 0
+        self.scenes, self.seams, self.frames = [], [], 0
         self._scene = dict(threshold=threshold, min_len=min_len, max_len=max_len)
         SceneCutter(1, **self._scene)                                       # bad options raise here, not at the first chunk
+        if isinstance(overlap, bool) or not isinstance(overlap, int) or not 0 <= overlap <= int(min_len):
+            raise ValueError(f"overlap must be a number of frames from 0 to min_len = {int(min_len)}, got {overlap!r}")
+        self._overlap = overlap
         self._gen = self._run(pipeline, iter(pieces), kwargs)
 
     def __iter__(self):
@@ -725,17 +747,19 @@ class SceneChunks:
     def _run(self, pipeline, pieces, kwargs):
         coefs = yuv_coefficients("bt601", True)         # the detector's luma: one table for every input, like its thresholds
         held, base, last, cutter = [], 0, None, None    # frames [base, self.frames) wait in `held`; `last`: the newest frame
+        tail = None                                     # the open seam: the scene before's rendering of this scene's first frames
 
-        def scene_clip(end):
+        def scene_clip(end, extra=0):
             """Take the frames [base, end) out of `held` as one contiguous clip.  The pieces are copied into it one by one and
-            let go as they are, so the scene and one piece exist at a time, not the scene twice."""
+            let go as they are, so the scene and one piece exist at a time, not the scene twice.  `extra`: the clip also gets a
+            copy of the frames [end, end + extra), which stay in `held` for the next scene."""
             nonlocal base
             n = end - base
             self.scenes.append((base, end))
             base = end
-            if len(held) == 1 and held[0].shape[2] == n and held[0].is_contiguous():
+            if extra == 0 and len(held) == 1 and held[0].shape[2] == n and held[0].is_contiguous():
                 return held.pop()
-            clip = held[0].new_empty(held[0].shape[:2] + (n,) + held[0].shape[3:])
+            clip = held[0].new_empty(held[0].shape[:2] + (n + extra,) + held[0].shape[3:])
             done = 0
             while done < n:
                 piece = held.pop(0)
@@ -745,7 +769,66 @@ class SceneChunks:
                     held.insert(0, piece[:, :, take:].clone())              # the next scene's first frames: less than a piece
                 done += take
                 del piece
+            for piece in held:                                              # known already: a cut has min_len >= extra frames behind it
+                take = min(piece.shape[2], n + extra - done)
+                clip[:, :, done:done + take] = piece[:, :, :take]
+                done += take
+                if done == n + extra:
+                    break
+            assert done == n + extra, "a forced cut without its look-ahead"
             return clip
+
+        def scene_chunks(end):
+            """The chunks of the scene [base, end).  After a forced cut its first `overlap` frames are the cross-fade of the scene
+            before's tail and this scene's head; before one, the clip runs `overlap` frames on and those are held, not emitted."""
+            nonlocal tail
+            extra = self._overlap if end in cutter.forced else 0
+            before, tail = tail, None
+            head = 0 if before is None else self._overlap
+            if head == 0 and extra == 0:
+                yield from upscale_clip_chunks(pipeline, scene_clip(end), **kwargs)
+                return
+            seam_at, total = base, end + extra - base
+            out_coefs, fmt, chroma = kwargs.get("coefs"), kwargs.get("fmt", "420"), kwargs.get("chroma", "replicate")
+            siting = output_siting(fmt, out_coefs.full_range, chroma) if out_coefs is not None else None
+            pos = got = kept = 0                        # frames of the clip seen, of the head gathered, of the tail kept
+            mine = after = None
+            for chunk in upscale_clip_chunks(pipeline, scene_clip(end, extra), seam=(head, extra), **kwargs):
+                fp32 = isinstance(chunk, torch.Tensor)
+                n = chunk.shape[0] if fp32 else chunk[0].shape[0]
+                h_n = max(0, min(pos + n, head) - pos)                      # [0, h_n) of the chunk: head; [t_0, n): tail
+                t_0 = min(n, max(0, total - extra - pos))
+                if h_n:
+                    if mine is None:
+                        mine = chunk.new_empty((head,) + chunk.shape[1:])
+                    mine[got:got + h_n] = chunk[:h_n]
+                    got += h_n
+                    if got == head:
+                        k = head
+                        with torch.no_grad(), E.device_guard(before):
+                            wa = torch.tensor([(k - j) / (k + 1) for j in range(k)], dtype=torch.float32).to(before.device)
+                            wb = torch.tensor([(j + 1) / (k + 1) for j in range(k)], dtype=torch.float32).to(before.device)
+                            blended = ops.frame_axpby_f32(before, mine, wa, wb, out=before)
+                            if out_coefs is not None:
+                                blended = postprocess_planes(blended, out_coefs, fmt, siting)
+                        self.seams.append(seam_at)
+                        before = mine = None
+                        for i in range(0, k, 3):
+                            yield blended[i:i + 3] if out_coefs is None else tuple(p[i:i + 3] for p in blended)
+                        del blended
+                if t_0 > h_n:
+                    part = chunk if (h_n, t_0) == (0, n) else chunk[h_n:t_0]
+                    yield postprocess_planes(part, out_coefs, fmt, siting) if fp32 and out_coefs is not None else part
+                    del part
+                if t_0 < n:
+                    if after is None:
+                        after = chunk.new_empty((extra,) + chunk.shape[1:])
+                    after[kept:kept + n - t_0] = chunk[t_0:]
+                    kept += n - t_0
+                pos += n
+                del chunk
+            assert pos == total and got == head and kept == extra, "a scene's chunks do not add up to its clip"
+            tail = after
 
         for piece in pieces:
             if piece.dim() != 5 or piece.shape[0] != 1 or piece.shape[1] != 3 or piece.shape[2] < 1:
@@ -765,15 +848,15 @@ class SceneChunks:
             self.frames += piece.shape[2]
             del piece
             for cut in cutter.push(sad, hist):
-                yield from upscale_clip_chunks(pipeline, scene_clip(cut), **kwargs)
+                yield from scene_chunks(cut)
         if cutter is None:
             raise ValueError("upscale_scenes_chunks: no frames")
         for cut in cutter.finish() + [self.frames]:
             if cut > base:
-                yield from upscale_clip_chunks(pipeline, scene_clip(cut), **kwargs)
+                yield from scene_chunks(cut)
 
 
-def upscale_scenes_chunks(pipeline, pieces, *, scene=(SCENE_THRESHOLD, SCENE_MIN_LEN, 0), **kwargs) -> SceneChunks:
+def upscale_scenes_chunks(pipeline, pieces, *, scene=(SCENE_THRESHOLD, SCENE_MIN_LEN, 0), overlap=0, **kwargs) -> SceneChunks:
     """`upscale_clip_chunks`, scene by scene (`--scenes auto`).  `pieces`: an iterator of (1,3,n,h,w) clips on the device, in
     order — a video read as far as it is needed; `scene` = (threshold, min_len, max_len) of `scene_cuts`; every other keyword is
     `upscale_clip_chunks`' and goes to it unchanged.  Each piece's statistics (`ops.clip_scene_stats`, with the last frame of the
@@ -783,5 +866,31 @@ def upscale_scenes_chunks(pipeline, pieces, *, scene=(SCENE_THRESHOLD, SCENE_MIN
     frames are dropped before more input is pulled.  Yields exactly what `upscale_clip_chunks` yields, scene after scene: a clip
     without a cut gives the chunks of `upscale_clip_chunks` on the whole clip bit for bit.  Held at once: the frames of the
     scene that is open (at most `max_len` when given) plus the piece that closed it and the min_len frames of look-ahead.
-    The result iterates and records `.scenes` / `.frames` (`SceneChunks`)."""
-    return SceneChunks(pipeline, pieces, scene, kwargs)
+    The result iterates and records `.scenes` / `.frames` (`SceneChunks`).
+
+    `overlap` = K > 0 (`--scene-overlap`) cross-fades the FORCED splits, those `max_len` makes in the middle of a shot
+    (`SceneCutter.forced`); 0, the default, is the path above, bit for bit.  A scene [s, c) that ends at a forced cut c runs as ONE
+    clip of the frames [s, c + K); its output for [c, c + K), the tail, is not emitted but held as fp32 frames at the delivery
+    size (after the colour fix and `out_size`, before the colour conversion).  The next scene starts at c as ever, and its first K
+    output frames, the head, taken at the same stage, are blended with the tail in one `ops.frame_axpby_f32` call:
+        out[c + j] = wa_j * tail[j] + wb_j * head[j],  wb_j = float32((j + 1) / (K + 1)),  wa_j = float32((K - j) / (K + 1)),
+    j = 0 .. K-1, every weight computed in double precision and rounded once, both products rounded to fp32 before the sum; with
+    `coefs` the result goes through `postprocess_planes` like a colour-fixed chunk.  A scene that ends at a detected cut or at the
+    end of the input is not extended: a detected cut stays hard.
+      - Both sides of a cross-fade are renderings of the same input frame; no content from across a real cut is ever mixed in.
+      - K <= min_len, else ValueError here, where bad scene options raise: a cut needs min_len known frames after it, so the K
+        frames behind a forced cut are already held when it is reported, the next scene has at least K frames, and a scene's head
+        and tail never overlap.
+      - The one `generator` is used in the order of the scenes, extended clips included.
+      - The result does not depend on how the input was cut into pieces.
+      - `.scenes` keeps the nominal ranges [c_i, c_i+1); `.seams` lists the forced cuts that were cross-faded.
+      - Every yielded chunk holds 1 to 3 frames, and the chunks add up to exactly the input's frames: a chunk that straddles a
+        seam comes out as its blended, plain and (withheld) tail parts.
+      - Chunks wholly outside a head or a tail keep their path (with `coefs`, the tile-by-tile conversion with no fp32 canvas);
+        one that holds a head or tail frame is assembled as fp32 frames whole (`upscale_clip_chunks(..., seam=(head, tail))`).
+    Held beside the above: K more input frames per open scene and K fp32 frames at the delivery size between two scenes (K*3*H*W*4
+    bytes: 100 MB per frame at 3840x2160), twice that while a head is gathered.  Each forced split sends K more frames through the
+    whole network, about K / max_len more work by the frame count (not measured).  The cross-fade is a linear dissolve between two
+    independent renderings: it spreads the change of the invented detail over K frames and softens detail there, it does not
+    remove the difference — and nobody has judged it on real footage."""
+    return SceneChunks(pipeline, pieces, scene, kwargs, overlap)
